@@ -20,12 +20,21 @@ proofs are one witness launch plus one nzcb_prove_batch call: --lanes proofs are
 flight on each GPU (lanes share the HBM-resident proving key; SURVEY.md §8e batch
 mode), so one proof's latency-bound phases overlap another's compute.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
 
 Rank 0 prints ONE JSON line. Each rank proves K proofs on its own GPU (weak
 scaling, no data-path collective); the timed region is bracketed by a barrier and
 device syncs, and the max over ranks is used.
+
+A plain run does what the headline figure needs: set-up, warm-up, the K timed proofs,
+the line. --dump-outputs DIR then writes the timed proofs and their public signals as
+DIR/proofs.npy and DIR/public_signals.npy (one float32 per byte; the passes and the
+blinding are functions of the proof index, so the same arguments give the same bytes).
+--full adds everything else around the same timed region: the single-proof latency and
+PCIe-inclusive proofs, the full-size checks of the timed proofs (nzcp kernel, pairing
+verifier), the isolated accumulation probe and roofline, memory per rank and the CPU
+baseline.
 """
 import argparse
 import hashlib
@@ -128,6 +137,29 @@ def pass_inputs(indices) -> bytes:
     return b"".join(nzcp.input_signals(nzcp.circuit_input(tbs, pass_data(i))) for i in indices)
 
 
+DUMP_MAX_BYTES = 60 << 20      # --dump-outputs writes at most this much array data (under 64 MB with headers)
+
+
+def dump_outputs(out_dir: str, proofs, rank: int) -> None:
+    """--dump-outputs: what the timed region's caller received, the (proof, public signals)
+    byte strings of this rank's timed proofs in proof order, as <name>.npy of shape
+    (proofs, bytes) with one float32 per byte (exact, so two builds compare bit for bit).
+    Rank 0 writes proofs.npy and public_signals.npy, rank r > 0 the same names with
+    `.rank<r>` before the suffix. A batch beyond DUMP_MAX_BYTES is cut to a seeded sample of its rows."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    if not proofs:  # a rank that held no proofs (--batch smaller than the world)
+        return
+    rows = np.arange(len(proofs))
+    row_bytes = 4 * sum(len(x) for x in proofs[0])
+    if row_bytes * len(proofs) > DUMP_MAX_BYTES:
+        rows = np.sort(np.random.default_rng(SEED).choice(len(proofs), DUMP_MAX_BYTES // row_bytes, replace=False))
+    tag = f".rank{rank}" if rank else ""
+    for k, name in enumerate(("proofs", "public_signals")):
+        a = np.array([np.frombuffer(proofs[i][k], dtype=np.uint8) for i in rows], dtype=np.float32)
+        np.save(os.path.join(out_dir, f"{name}{tag}.npy"), a.reshape(len(rows), -1))
+
+
 def accumulate_probe(n_points: int, device: int, reps: int = 10) -> dict:
     """The dominant kernel alone on the chip: `reps` fixed-base MSMs of the prover's size
     (n + 6 points, random scalars, the same c = 20 table schedule) with HIP events around
@@ -147,6 +179,67 @@ def accumulate_probe(n_points: int, device: int, reps: int = 10) -> dict:
         nzcb.dev_free(bases)
         eng.close()
     return ph
+
+
+def accumulation_roofline(n: int, timed_stats, single_stats, probe) -> dict:
+    """--full: the line's `roofline` entry for the dominant kernel, from the timed region's kernel
+    statistics (ms, launches, points, bucket entries), the single-lane proof's (ms, launches) and
+    the isolated probe's phases (None when skipped)."""
+    kms, klaunch, kpoints, kentries = timed_stats
+    lat_kms, lat_klaunch = single_stats
+    # the accumulation kernel over the timed region (HIP events on the MSM streams;
+    # --lanes proofs share the chip, so these launches overlap other kernels)
+    shared_ms = kms / max(klaunch, 1)
+    pts_per_launch = kpoints / max(klaunch, 1)
+    ent_per_launch = kentries / max(klaunch, 1)
+    # the same kernel alone on the chip, same size and schedule: its duration is the
+    # roofline's launch time (profiles/: the last 10 accumulation launches of the trace)
+    iso_ms = probe["accumulate"] if probe else None
+    launch_ms = iso_ms or shared_ms
+    # the probe's launch: its own entries (random scalars: ~15 per point); the timed
+    # region's average also holds the A, B, C MSMs of small witness values
+    probe_entries = probe.get("entries") if probe else None
+    launch_entries = probe_entries or ent_per_launch
+    launch_points = (n + 6) if probe else pts_per_launch
+    mads_t = MADS_PER_ENTRY * launch_entries / (launch_ms / 1e3) / 1e12 if launch_ms else 0.0
+    hbm_gbs = MSM_BYTES_PER_POINT * launch_points / (launch_ms / 1e3) / 1e9 if launch_ms else 0.0
+    # HBM traffic per launch is a committed PMC measurement (two separate rocprofv3 --pmc
+    # passes, FETCH_SIZE and WRITE_SIZE, tools/profile_round.sh), not this run's: the line
+    # names the file and the run it came from (VERDICT r5 item 8)
+    traffic = traffic_source = None
+    tf = os.environ.get("NZCB_TRAFFIC_JSON", os.path.join(ROOT, "profiles", "accumulate_traffic.json"))
+    if tf and os.path.exists(tf):
+        with open(tf) as f:
+            tj = json.load(f)
+        traffic = tj.get("bytes_per_launch")
+        traffic_source = {"file": os.path.relpath(tf, ROOT), "measured": tj.get("source", "round 5 profile set"),
+                          "in_this_run": False}
+    return {
+        "kernel": "msm_accumulate29_kernel (fixed-base Pippenger bucket accumulation, c=20, 2^21+6 points)",
+        # VALU integer-multiply issue governs this kernel (SURVEY.md §8d); the contract's
+        # hbm/mfma vocabulary has no word for it, and there is no MFMA in modular arithmetic
+        "bound": "valu",
+        "achieved": round(mads_t, 3),
+        "peak": round(MAD_PEAK_T, 2),
+        "unit": "T v_mad_u64_u32 lane-ops/s",
+        "frac": round(mads_t / MAD_PEAK_T, 4),
+        "traffic": traffic,
+        "traffic_source": traffic_source,
+        "avg_launch_ms": round(launch_ms, 4),
+        "launch_ms_basis": "isolated launches (accumulate_probe, HIP events)" if iso_ms
+                           else "timed region, shared chip (probe skipped)",
+        "timed_region_avg_launch_ms": round(shared_ms, 4),
+        "single_proof_avg_launch_ms": round(lat_kms / max(lat_klaunch, 1), 4),
+        "launches_timed": int(klaunch),
+        "points_per_launch": int(launch_points),
+        "bucket_entries_per_launch": int(launch_entries),
+        "timed_region_avg_entries_per_launch": int(ent_per_launch),
+        "mads_per_entry": MADS_PER_ENTRY,
+        "hbm": {"algorithmic_bytes_per_launch": int(MSM_BYTES_PER_POINT * launch_points),
+                "bytes_per_point": MSM_BYTES_PER_POINT, "achieved_GBs": round(hbm_gbs, 2),
+                "peak_GBs": HBM_PEAK_GBS, "frac": round(hbm_gbs / HBM_PEAK_GBS, 5)},
+        "probe_phase_ms": {k: round(v, 4) for k, v in probe.items() if k != "entries"} if probe else None,
+    }
 
 
 def cpu_model() -> str:
@@ -242,8 +335,14 @@ def main():
     ap.add_argument("--msm-split", action="store_true",
                     help="configs[4] across ranks: rank 0 proves --steps proofs one at a time, every commitment "
                          "MSM split by point range over all ranks (scatter of scalar slices + gather of partials)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-probe", action="store_true", help="skip the isolated accumulation-kernel probe")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write their proofs and public signals as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: single-proof latency, full-size "
+                         "checks of the timed proofs, accumulation probe and roofline, memory, CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-probe", action="store_true",
+                    help="with --full: skip the isolated accumulation-kernel probe")
     ap.add_argument("--launch-check", action="store_true",
                     help="start the ranks, report world size and devices, and exit (no GPU work)")
     args = ap.parse_args()
@@ -311,31 +410,33 @@ def main():
             torch.cuda.synchronize(device)
             dist.barrier()
 
-    # one pass's witness for the single-proof latency and the PCIe-inclusive rate
-    # (neither is the reported value) and the CPU baseline's sample
-    prover.upload_inputs(pass_inputs([999]))
-    (w0,) = prover.witness_staged(1)
-    nwit = prover.n_witness
-    dev_w = nzcb.dev_alloc(nwit * 32)
-    nzcb.d2d(dev_w, w0, nwit * 32)
-    wit_host = nzcb.d2h(dev_w, nwit * 32)
-    ctx.prove_device_raw(dev_w, nwit, blinding_for(998))
-    # the latency proof runs without kernel statistics (no timing events), then one more
-    # proof with them gives the per-phase GPU times and the accumulation's single-lane launch
-    # (the median of 5: one proof's wall time varies by ~0.5 ms from run to run)
-    lat = []
-    for k in range(5):
-        t_l = time.perf_counter()
-        ctx.prove_device_raw(dev_w, nwit, blinding_for(997 - 10 * k))
-        lat.append((time.perf_counter() - t_l) * 1e3)
-    latency_ms = sorted(lat)[len(lat) // 2]
-    ctx.kernel_stats(1)
-    ctx.prove_device_raw(dev_w, nwit, blinding_for(996))
-    lat_kms, lat_klaunch, _, _ = ctx.kernel_stats(0)  # one proof in flight: the kernel nearly alone
-    single_timings = ctx.last_timings()
-    t_h = time.perf_counter()
-    ctx.prove_witness_raw(wit_host, blinding_for(999))
-    pcie_ms = (time.perf_counter() - t_h) * 1e3
+    dev_w = None
+    if args.full:
+        # one pass's witness for the single-proof latency and the PCIe-inclusive rate
+        # (neither is the reported value) and the CPU baseline's sample
+        prover.upload_inputs(pass_inputs([999]))
+        (w0,) = prover.witness_staged(1)
+        nwit = prover.n_witness
+        dev_w = nzcb.dev_alloc(nwit * 32)
+        nzcb.d2d(dev_w, w0, nwit * 32)
+        wit_host = nzcb.d2h(dev_w, nwit * 32)
+        ctx.prove_device_raw(dev_w, nwit, blinding_for(998))
+        # the latency proof runs without kernel statistics (no timing events), then one more
+        # proof with them gives the per-phase GPU times and the accumulation's single-lane launch
+        # (the median of 5: one proof's wall time varies by ~0.5 ms from run to run)
+        lat = []
+        for k in range(5):
+            t_l = time.perf_counter()
+            ctx.prove_device_raw(dev_w, nwit, blinding_for(997 - 10 * k))
+            lat.append((time.perf_counter() - t_l) * 1e3)
+        latency_ms = sorted(lat)[len(lat) // 2]
+        ctx.kernel_stats(1)
+        ctx.prove_device_raw(dev_w, nwit, blinding_for(996))
+        lat_kms, lat_klaunch, _, _ = ctx.kernel_stats(0)  # one proof in flight: the kernel nearly alone
+        single_timings = ctx.last_timings()
+        t_h = time.perf_counter()
+        ctx.prove_witness_raw(wit_host, blinding_for(999))
+        pcie_ms = (time.perf_counter() - t_h) * 1e3
     msm_devices = [int(x) for x in args.msm_devices.split(",") if x.strip() != ""]
     if msm_devices:
         ctx.set_msm_devices(msm_devices)
@@ -408,20 +509,24 @@ def main():
             backend_range[2].close()
         nzcb.dev_free(backend_range[1])
     assert len({p for p, _ in proofs}) == len(mine)  # distinct passes -> distinct proofs
-    # full-size checks outside the timed region: every proof's public signals equal its
-    # pass's outputs from the independent nzcp kernel (csrc/nzcp.hip, bit-exact against
-    # the restatement pinned by the reference's KATs), and the pairing verifier accepts
-    # the first and last proof of the batch
-    records = nzcb.nzcp_witness(pass_inputs(mine), len(mine), nzcb.NZCP_LIVE, device) if mine else []
-    pubs_ok = all(r["status"] == 0 and [int.from_bytes(pub[32 * k:32 * k + 32], "little") for k in range(3)] == r["out"]
-                  for (_, pub), r in zip(proofs, records))
-    verified = pubs_ok and all(nzcb.verify(ctx.vk, proofs[i][0], proofs[i][1])
-                               for i in ({0, len(proofs) - 1} if proofs else ()))
-    t_w = time.perf_counter()
-    prover.witness_staged(len(mine))
-    witness_ms = (time.perf_counter() - t_w) * 1e3
-    mem = rank_memory(device, dist)
-    probe =accumulate_probe(n + 6, device) if rank == 0 and not args.no_probe else None
+    if args.dump_outputs and not (split and rank != 0):
+        dump_outputs(args.dump_outputs, proofs, rank)
+    verified = None  # checked by --full only
+    if args.full:
+        # full-size checks outside the timed region: every proof's public signals equal its
+        # pass's outputs from the independent nzcp kernel (csrc/nzcp.hip, bit-exact against
+        # the restatement pinned by the reference's KATs), and the pairing verifier accepts
+        # the first and last proof of the batch
+        records = nzcb.nzcp_witness(pass_inputs(mine), len(mine), nzcb.NZCP_LIVE, device) if mine else []
+        pubs_ok = all(r["status"] == 0 and [int.from_bytes(pub[32 * k:32 * k + 32], "little") for k in range(3)] == r["out"]
+                      for (_, pub), r in zip(proofs, records))
+        verified = pubs_ok and all(nzcb.verify(ctx.vk, proofs[i][0], proofs[i][1])
+                                   for i in ({0, len(proofs) - 1} if proofs else ()))
+        t_w = time.perf_counter()
+        prover.witness_staged(len(mine))
+        witness_ms = (time.perf_counter() - t_w) * 1e3
+        mem = rank_memory(device, dist)
+        probe = accumulate_probe(n + 6, device) if rank == 0 and not args.no_probe else None
     elapsed = max_over_ranks(elapsed, dist, f"cuda:{device}" if backend == "nccl" else "cpu")
     total_proofs = args.steps if split else (args.batch if args.batch else args.steps * world)
     steps = len(shard(args.batch, 0, world)) if args.batch and not split else args.steps
@@ -429,39 +534,6 @@ def main():
     ms_step = elapsed / steps * 1e3
 
     if rank == 0:
-        # the accumulation kernel over the timed region (HIP events on the MSM streams;
-        # --lanes proofs share the chip, so these launches overlap other kernels)
-        shared_ms = kms / max(klaunch, 1)
-        pts_per_launch = kpoints / max(klaunch, 1)
-        ent_per_launch = kentries / max(klaunch, 1)
-        # the same kernel alone on the chip, same size and schedule: its duration is the
-        # roofline's launch time (profiles/: the last 10 accumulation launches of the trace)
-        iso_ms = probe["accumulate"] if probe else None
-        launch_ms = iso_ms or shared_ms
-        # the probe's launch: its own entries (random scalars: ~15 per point); the timed
-        # region's average also holds the A, B, C MSMs of small witness values
-        probe_entries = probe.get("entries") if probe else None
-        launch_entries = probe_entries or ent_per_launch
-        launch_points = (n + 6) if probe else pts_per_launch
-        mads_t = MADS_PER_ENTRY * launch_entries / (launch_ms / 1e3) / 1e12 if launch_ms else 0.0
-        hbm_gbs = MSM_BYTES_PER_POINT * launch_points / (launch_ms / 1e3) / 1e9 if launch_ms else 0.0
-        # HBM traffic per launch is a committed PMC measurement (two separate rocprofv3 --pmc
-        # passes, FETCH_SIZE and WRITE_SIZE, tools/profile_round.sh), not this run's: the line
-        # names the file and the run it came from
-        traffic = traffic_source = None
-        tf = os.environ.get("NZCB_TRAFFIC_JSON", os.path.join(ROOT, "profiles", "accumulate_traffic.json"))
-        if tf and os.path.exists(tf):
-            with open(tf) as f:
-                tj = json.load(f)
-            traffic = tj.get("bytes_per_launch")
-            traffic_source = {"file": os.path.relpath(tf, ROOT), "measured": tj.get("source", "round 5 profile set"),
-                              "in_this_run": False}
-        cpu = None
-        if world == 1 and not args.no_cpu_baseline:
-            try:
-                cpu = cpu_baseline_sample(zkey_raw, nzcplive.wtns_file(wit_host), n)
-            except Exception as e:  # reported, never silently replaced
-                cpu = {"value": None, "unit": "proofs/s", "cores": 0, "kind": "port", "sample": f"failed: {e}"}
         proof_gbs = PROOF_BYTES_PER_N * n / (ms_step / 1e3) / 1e9
         # ranks sharing a device (the one-GPU rehearsal, NZCB_BENCH_DEVICE) are not that many
         # GPUs: n_gpus counts distinct devices and the line says it is a rehearsal
@@ -500,56 +572,42 @@ def main():
                 "rank_devices": rank_devices,
                 "dist_backend": backend if dist is not None else None,
             },
-            "roofline": {
-                "kernel": "msm_accumulate29_kernel (fixed-base Pippenger bucket accumulation, c=20, 2^21+6 points)",
-                # VALU integer-multiply issue governs this kernel; the contract's
-                # hbm/mfma vocabulary has no word for it, and there is no MFMA in modular arithmetic
-                "bound": "valu",
-                "achieved": round(mads_t, 3),
-                "peak": round(MAD_PEAK_T, 2),
-                "unit": "T v_mad_u64_u32 lane-ops/s",
-                "frac": round(mads_t / MAD_PEAK_T, 4),
-                "traffic": traffic,
-                "traffic_source": traffic_source,
-                "avg_launch_ms": round(launch_ms, 4),
-                "launch_ms_basis": "isolated launches (accumulate_probe, HIP events)" if iso_ms
-                                   else "timed region, shared chip (probe skipped)",
-                "timed_region_avg_launch_ms": round(shared_ms, 4),
-                "single_proof_avg_launch_ms": round(lat_kms / max(lat_klaunch, 1), 4),
-                "launches_timed": int(klaunch),
-                "points_per_launch": int(launch_points),
-                "bucket_entries_per_launch": int(launch_entries),
-                "timed_region_avg_entries_per_launch": int(ent_per_launch),
-                "mads_per_entry": MADS_PER_ENTRY,
-                "hbm": {"algorithmic_bytes_per_launch": int(MSM_BYTES_PER_POINT * launch_points),
-                        "bytes_per_point": MSM_BYTES_PER_POINT, "achieved_GBs": round(hbm_gbs, 2),
-                        "peak_GBs": HBM_PEAK_GBS, "frac": round(hbm_gbs / HBM_PEAK_GBS, 5)},
-                "probe_phase_ms": {k: round(v, 4) for k, v in probe.items() if k != "entries"} if probe else None,
-            },
             "proof_roofline": {
                 "algorithmic_bytes": PROOF_BYTES_PER_N * n,
                 "achieved_GBs": round(proof_gbs, 2),
                 "frac": round(proof_gbs / HBM_PEAK_GBS, 5),
             },
             "rehearsal": n_devices != world,
-            "proofs_verified": verified,
-            "witness_program_ms_per_batch": round(witness_ms, 3),
-            "single_proof_latency_ms": round(latency_ms, 3),
-            "single_proof_latency_ms_runs": [round(x, 3) for x in lat],
-            "phase_ms_single_proof": {k: round(v, 3) for k, v in single_timings.items()},
-            "pcie_inclusive_ms": round(pcie_ms, 3),
             "setup_s": round(setup_s, 2),
-            "memory_per_rank": mem,
-            "cpu_baseline": cpu,
+            "full": args.full,
         }
-        if not verified:  # never report a rate for proofs that do not verify
+        if args.full:
+            cpu = None
+            if world == 1 and not args.no_cpu_baseline:
+                try:
+                    cpu = cpu_baseline_sample(zkey_raw, nzcplive.wtns_file(wit_host), n)
+                except Exception as e:  # reported, never silently replaced
+                    cpu = {"value": None, "unit": "proofs/s", "cores": 0, "kind": "port", "sample": f"failed: {e}"}
+            line.update({
+                "roofline": accumulation_roofline(n, (kms, klaunch, kpoints, kentries), (lat_kms, lat_klaunch), probe),
+                "proofs_verified": verified,
+                "witness_program_ms_per_batch": round(witness_ms, 3),
+                "single_proof_latency_ms": round(latency_ms, 3),
+                "single_proof_latency_ms_runs": [round(x, 3) for x in lat],
+                "phase_ms_single_proof": {k: round(v, 3) for k, v in single_timings.items()},
+                "pcie_inclusive_ms": round(pcie_ms, 3),
+                "memory_per_rank": mem,
+                "cpu_baseline": cpu,
+            })
+        if args.full and not verified:  # never report a rate for proofs that do not verify
             line["value"] = None
             line["error"] = "proofs_verified is false: public signals differ from the nzcp records or a proof " \
                             "failed the pairing check"
         print(json.dumps(line), flush=True)
-        if not verified:
+        if args.full and not verified:
             sys.exit(3)
-    nzcb.dev_free(dev_w)
+    if dev_w is not None:
+        nzcb.dev_free(dev_w)
     prover.close()
     ctx.close()
     nzcb.free_ptr(zkey_raw[0])

@@ -8,6 +8,7 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p gpurun_out
 out=gpurun_out/${tag}_multi.log
 : > $out
+BENCH_ARGS="--full ${BENCH_ARGS:-}"  # the single-proof latency printed below is a --full figure
 for rep in 1 2; do
   for cfg in "$@"; do
     env $cfg timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-probe ${BENCH_ARGS:-} > gpurun_out/${tag}_bench.log 2>&1 || exit $?

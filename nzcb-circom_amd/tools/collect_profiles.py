@@ -47,7 +47,7 @@ def valu_by_kernel(path):
         c, v = agg.get(k, (0, 0.0))
         agg[k] = (c + 1, v + float(r["Counter_Value"]))
     tot = sum(v for _, v in agg.values())
-    lines = ["# rocprofv3 --pmc SQ_INSTS_VALU SQ_WAVES -- python3 bench.py --lanes 1 --steps 4 --warmup 1 "
+    lines = ["# rocprofv3 --pmc SQ_INSTS_VALU SQ_WAVES -- python3 bench.py --full --lanes 1 --steps 4 --warmup 1 "
              "--no-cpu-baseline --no-probe",
              f"# dispatches from the first proof on (context setup excluded): {nproofs} proofs (latency/PCIe runs, "
              f"warm-up, timed)",
@@ -107,7 +107,7 @@ def main():
     line = [l for l in open(os.path.join(src, f"{a.prof}_bench.log")) if l.startswith('{"metric"')][-1]
     bench = json.loads(line)
     with open(os.path.join(out, f"{a.prefix}_bench_line.txt"), "w") as f:
-        f.write("# rocprofv3 --kernel-trace --stats -- python3 bench.py   (defaults)\n" + line)
+        f.write("# rocprofv3 --kernel-trace --stats -- python3 bench.py --full   (defaults)\n" + line)
     launches = bench["roofline"]["launches_timed"]
     probe = 10   # bench.py accumulate_probe: 2 + 1 warm-up and 10 timed launches, the last of the run
     ts = os.path.join(HERE, "trace_summary.py")
@@ -130,7 +130,7 @@ def main():
         "kernel": "msm_accumulate29_kernel<true> (fixed-base bucket accumulation: LDS-staged indices, paired "
                   "products; 2^21+6-point MSM of random scalars at the default window, c = %d: bench.py's probe, the "
                   "last 10 launches of each pass)" % WINDOW,
-        "command": "rocprofv3 --pmc FETCH_SIZE | --pmc WRITE_SIZE (separate passes) -- python3 bench.py "
+        "command": "rocprofv3 --pmc FETCH_SIZE | --pmc WRITE_SIZE (separate passes) -- python3 bench.py --full "
                    "--no-cpu-baseline --steps 8",
         "counters_kb_per_launch": {"FETCH_SIZE": {"launches": nf, "avg_kb_per_launch": round(fetch_kb, 1)},
                                    "WRITE_SIZE": {"launches": nw, "avg_kb_per_launch": round(write_kb, 1)}},
@@ -163,7 +163,7 @@ def main():
         txt = subprocess.run([sys.executable, os.path.join(HERE, "phase_kernels.py"), lane1, "--proofs", "4"],
                              check=True, capture_output=True, text=True).stdout
         with open(os.path.join(out, f"{a.prefix}_single_lane_phases.txt"), "w") as f:
-            f.write("# rocprofv3 --kernel-trace --marker-trace -- python3 bench.py --lanes 1 --steps 6 --warmup 2 "
+            f.write("# rocprofv3 --kernel-trace --marker-trace -- python3 bench.py --full --lanes 1 --steps 6 --warmup 2 "
                     "--no-cpu-baseline --no-probe\n" + txt)
     print(psumm + summ)
 

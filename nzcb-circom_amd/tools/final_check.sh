@@ -18,14 +18,14 @@ step smoke
 timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1 || exit $?
 tail -1 $O/smoke.log
 step bench
-timeout -k 10 600 python3 -u bench.py > $O/bench.log 2>&1 || exit $?
+timeout -k 10 600 python3 -u bench.py --full > $O/bench.log 2>&1 || exit $?
 grep '^{"metric"' $O/bench.log | tail -1 | cut -c1-400
 PREV=nzcb-circom_amd/lib/ab/libnzcb_r5.so
 if [ -f $PREV ]; then
   for cfg in r6 r5 r6b r5b; do
     L=nzcb-circom_amd/lib/libnzcb.so; [ ${cfg:0:2} = r5 ] && L=$PREV
     step "ab $cfg"
-    NZCB_LIB=$L timeout -k 10 300 python3 -u bench.py --steps 300 --warmup 5 --no-cpu-baseline --no-probe > $O/ab_$cfg.log 2>&1 || exit $?
+    NZCB_LIB=$L timeout -k 10 300 python3 -u bench.py --full --steps 300 --warmup 5 --no-cpu-baseline --no-probe > $O/ab_$cfg.log 2>&1 || exit $?
     python3 -c "import json;d=json.loads([l for l in open('$O/ab_$cfg.log') if l.startswith('{')][-1]);print('$cfg', d['value'], d['ms_per_step'], d['single_proof_latency_ms'])"
   done
 fi

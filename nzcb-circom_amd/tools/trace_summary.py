@@ -17,7 +17,7 @@ def main():
                     help="with --last: end the window before the kernel's last SKIP launches (e.g. a probe)")
     ap.add_argument("--before-last", metavar="NAME", default=None,
                     help="with --last: end the window before the last launch of a kernel whose name contains NAME "
-                         "(bench.py's probe starts with k_fixed_base, its random bases)")
+                         "(bench.py --full's probe starts with k_fixed_base, its random bases)")
     ap.add_argument("--durations", action="store_true",
                     help="with --last: also print the average duration of the KERNEL launches in the window")
     a = ap.parse_args()

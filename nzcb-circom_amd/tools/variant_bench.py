@@ -9,7 +9,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 power = sys.argv[1] if len(sys.argv) > 1 else "21"
 for lib in sorted(glob.glob(os.path.join(ROOT, "nzcb-circom_amd", "lib", "variants", "*.so"))):
     env = dict(os.environ, NZCB_LIB=lib)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--power", power, "--steps", "3",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--power", power, "--steps", "3",
                         "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=300)
     line = [l for l in p.stdout.splitlines() if l.startswith("{")]
     if not line:
