@@ -106,14 +106,20 @@ int nzcb_engine_msm_fixed_dev(nzcb_engine* e, const void* bases, size_t n_table,
                               int scalars_mont, uint8_t* out_affine, nzcb_err* err);
 /* The same with the table's window (16..20, 0 = the PTau tables' default) and schedule:
  * sparse = 1 is the Lagrange-basis table's (device-derived accumulation chunk, log-depth
- * carry trees; msm.hip dyn_chunk). */
+ * carry trees; msm.hip dyn_chunk), sparse = 0 the dense one (fixed 48-entry chunk). fold = 1
+ * builds the table as the prover builds its PTau tables (MsmBaseTable::mont_folded: rows of
+ * 2^-256 B_i): the digits are then taken from the scalars' raw 256-bit Montgomery integers m_i
+ * and the result is sum (m_i 2^-256 mod r) B_i; it needs scalars_mont = 1 (NZCB_ERR_ARG
+ * otherwise). */
 int nzcb_engine_msm_table_dev(nzcb_engine* e, const void* bases, size_t n_table, const void* scalars, size_t n,
-                              int scalars_mont, int window, int sparse, uint8_t* out_affine, nzcb_err* err);
+                              int scalars_mont, int window, int sparse, int fold, uint8_t* out_affine,
+                              nzcb_err* err);
 /* `sets` (1..3) MSMs of n scalars each (device pointers scalars[0..sets)) over ONE Lagrange-window
  * table of the first n_table bases in one schedule (msm.hip msm_enqueue_sets: the prover's A, B,
- * C commitments since round 6); out_affine: sets x 64 bytes. */
+ * C commitments since round 6); sparse = 0 is the schedule the prover runs by default, sparse = 1
+ * the one NZCB_SPARSE=1 selects. out_affine: sets x 64 bytes (n = 0: `sets` infinities). */
 int nzcb_engine_msm_sets_dev(nzcb_engine* e, const void* bases, size_t n_table, const void* const* scalars, int sets,
-                             size_t n, int scalars_mont, uint8_t* out_affine, nzcb_err* err);
+                             size_t n, int scalars_mont, int sparse, uint8_t* out_affine, nzcb_err* err);
 /* Per-phase MSM timing (HIP events, average over reps after three warm-up runs):
  * out[0] wall ms, out[1..7] keys, sort, offsets, accumulate, finalize, reduce, sums,
  * out[8] table build ms (fixed_base only), out[9] bucket entries per MSM (nonzero digits),

@@ -326,18 +326,18 @@ int nzcb_engine_time_msm(nzcb_engine* e, const void* bases, const void* scalars,
 
 int nzcb_engine_msm_fixed_dev(nzcb_engine* e, const void* bases, size_t n_table, const void* scalars, size_t n,
                               int scalars_mont, uint8_t* out_affine, nzcb_err* err) {
-  return nzcb_engine_msm_table_dev(e, bases, n_table, scalars, n, scalars_mont, 0, 0, out_affine, err);
+  return nzcb_engine_msm_table_dev(e, bases, n_table, scalars, n, scalars_mont, 0, 0, 0, out_affine, err);
 }
 
 int nzcb_engine_msm_table_dev(nzcb_engine* e, const void* bases, size_t n_table, const void* scalars, size_t n,
-                              int scalars_mont, int window, int sparse, uint8_t* out_affine, nzcb_err* err) {
+                              int scalars_mont, int window, int sparse, int fold, uint8_t* out_affine, nzcb_err* err) {
   NZ_GUARD_BEGIN
   Engine& g = e->eng;
   NZ_HIP(hipSetDevice(g.device));
   if (n > n_table) throw Error(NZCB_ERR_ARG, "msm larger than its base table");
   if (window && (window < 16 || window > 20)) throw Error(NZCB_ERR_ARG, "msm table window: 16..20");
   MsmBaseTable t;
-  t.build((const G1Affine*)bases, n_table, window ? window : fixed_base_window(), g.stream);
+  t.build((const G1Affine*)bases, n_table, window ? window : fixed_base_window(), g.stream, fold != 0);
   t.sparse = sparse != 0;
   MsmScratch sc;
   sc.init(n ? n : 1, true);
@@ -348,7 +348,7 @@ int nzcb_engine_msm_table_dev(nzcb_engine* e, const void* bases, size_t n_table,
 }
 
 int nzcb_engine_msm_sets_dev(nzcb_engine* e, const void* bases, size_t n_table, const void* const* scalars, int sets,
-                             size_t n, int scalars_mont, uint8_t* out_affine, nzcb_err* err) {
+                             size_t n, int scalars_mont, int sparse, uint8_t* out_affine, nzcb_err* err) {
   NZ_GUARD_BEGIN
   Engine& g = e->eng;
   NZ_HIP(hipSetDevice(g.device));
@@ -356,10 +356,10 @@ int nzcb_engine_msm_sets_dev(nzcb_engine* e, const void* bases, size_t n_table, 
   if (sets < 1 || sets > 3 || !scalars) throw Error(NZCB_ERR_ARG, "msm sets: 1..3 scalar vectors");
   MsmBaseTable t;
   t.build((const G1Affine*)bases, n_table, lagrange_window(), g.stream);
-  t.sparse = true;
+  t.sparse = sparse != 0;
   MsmScratch sc;
   sc.init(n ? n : 1, true, 3, false);
-  G1xyzz r[3];
+  G1xyzz r[3] = {G1xyzz::inf(), G1xyzz::inf(), G1xyzz::inf()};
   msm_enqueue_sets(sc, (const Fr* const*)scalars, sets, n, scalars_mont != 0, g.stream, &t);
   msm_finish_sets(sc, g.stream, r);
   for (int k = 0; k < sets; k++) affine_out(r[k], out_affine + 64 * k);

@@ -1704,7 +1704,10 @@ static void msm_enqueue_impl(MsmScratch& sc, const G1Affine* bases, const Fr* co
         sc.enqueue_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
   } enqueue_clock{sc, t_enq};
+  if (msets < 1 || msets > kMaxSets || (msets > 1 && (!table || msets > sc.max_lsets)))
+    throw Error(NZCB_ERR_ARG, "msm sets: 1..3 over a table, within the scratch's sizing");
   sc.cur_n = n;
+  sc.cur_msets = table ? msets : 1;  // msm_finish_sets fills this many results, at n = 0 too
   if (n == 0) return;
   if (!sc.done) NZ_HIP(hipEventCreateWithFlags(&sc.done, hipEventDisableTiming));
   if (n > sc.max_points) throw Error(NZCB_ERR_ARG, "msm larger than scratch");
@@ -1714,8 +1717,6 @@ static void msm_enqueue_impl(MsmScratch& sc, const G1Affine* bases, const Fr* co
     throw Error(NZCB_ERR_ARG, "msm scratch was not sized for the fixed-base schedule");
   // a folded table takes the Montgomery form's integer as the scalar (msm_table_kernel)
   const int mdig = (mont && !(table && table->mont_folded)) ? 1 : 0;
-  if (msets < 1 || msets > kMaxSets || (msets > 1 && (!table || msets > sc.max_lsets)))
-    throw Error(NZCB_ERR_ARG, "msm sets: 1..3 over a table, within the scratch's sizing");
   const MsmPlan p = make_plan(n, table, msets);
 #ifdef NZCB_MSM_STATS
   if (table && !table->mont_folded) {  // scalar census (diagnostics build): nonzero c-bit digits of

@@ -206,9 +206,9 @@ def load(path: str | None = None):
         "nzcb_engine_msm_fixed_dev": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_int, u8p,
                                               POINTER(_Err)]),
         "nzcb_engine_msm_table_dev": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_int, c_int, c_int,
-                                              u8p, POINTER(_Err)]),
+                                              c_int, u8p, POINTER(_Err)]),
         "nzcb_engine_msm_sets_dev": (c_int, [c_void_p, c_void_p, c_size_t, POINTER(c_void_p), c_int, c_size_t, c_int,
-                                             u8p, POINTER(_Err)]),
+                                             c_int, u8p, POINTER(_Err)]),
         "nzcb_plonk_setup": (c_int, [ctypes.c_char_p, c_size_t, ctypes.c_char_p, c_size_t, c_int, POINTER(POINTER(c_uint8)),
                                      POINTER(c_size_t), POINTER(_Err)]),
         "nzcb_nzcp_input_signals": (c_size_t, [POINTER(NzcpParams)]),
@@ -406,28 +406,33 @@ class Engine:
         return d
 
     def msm_fixed_dev(self, dev_bases: int, n_table: int, dev_scalars: int, n: int, scalars_mont: bool,
-                      window: int = 0, sparse: bool = False) -> bytes:
+                      window: int = 0, sparse: bool = False, fold: bool = False) -> bytes:
         """Fixed-base (shifted-table) MSM of the first n of n_table device bases; window 0 = the
-        PTau tables' default, sparse = the Lagrange table's schedule (msm.hip dyn_chunk)."""
+        PTau tables' default, sparse = the Lagrange table's schedule (msm.hip dyn_chunk), fold =
+        the prover's 2^-256-folded PTau table: the scalars' raw Montgomery integers m_i are the
+        digit source and the result is sum (m_i 2^-256 mod r) B_i (needs scalars_mont)."""
         out = _out(64)
         err = _Err()
-        if window or sparse:
+        if window or sparse or fold:
             _check(self.lib.nzcb_engine_msm_table_dev(self.h, dev_bases, n_table, dev_scalars, n, int(scalars_mont),
-                                                      int(window), int(sparse), out, ctypes.byref(err)), err)
+                                                      int(window), int(sparse), int(fold), out, ctypes.byref(err)),
+                   err)
         else:
             _check(self.lib.nzcb_engine_msm_fixed_dev(self.h, dev_bases, n_table, dev_scalars, n, int(scalars_mont),
                                                       out, ctypes.byref(err)), err)
         return bytes(out)
 
-    def msm_sets_dev(self, dev_bases: int, n_table: int, dev_scalars: list, n: int, scalars_mont: bool) -> list:
+    def msm_sets_dev(self, dev_bases: int, n_table: int, dev_scalars: list, n: int, scalars_mont: bool, *,
+                     sparse: bool) -> list:
         """len(dev_scalars) (1..3) MSMs of n scalars over one Lagrange-window table in one schedule
-        (the prover's A, B, C commitments): one 64-byte affine result per set."""
+        (the prover's A, B, C commitments): one 64-byte affine result per set. sparse=False is the
+        schedule the prover runs by default, sparse=True the one NZCB_SPARSE=1 selects."""
         k = len(dev_scalars)
         out = _out(64 * k)
         err = _Err()
         arr = (c_void_p * k)(*dev_scalars)
-        _check(self.lib.nzcb_engine_msm_sets_dev(self.h, dev_bases, n_table, arr, k, n, int(scalars_mont), out,
-                                                 ctypes.byref(err)), err)
+        _check(self.lib.nzcb_engine_msm_sets_dev(self.h, dev_bases, n_table, arr, k, n, int(scalars_mont),
+                                                 int(bool(sparse)), out, ctypes.byref(err)), err)
         return [bytes(out)[64 * i:64 * i + 64] for i in range(k)]
 
     def msm_dev(self, dev_bases: int, dev_scalars: int, n: int, scalars_mont: bool) -> bytes:

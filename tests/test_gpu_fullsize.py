@@ -125,7 +125,8 @@ def test_msm_2p21_witness_scalars_schedules_agree():
     digits are zero and the bucketing drops them, and bucket 0 (|digit| = 1) holds ~40 %
     of the entries (long carry runs through the finalize's workgroup path). The fixed-base
     schedule equals the generic one, which keeps every digit, and splits linearly; the sparse
-    schedule the prover uses for these scalars (round 6) gives the same point."""
+    schedule (round 6; NZCB_SPARSE=1) gives the same point, and so do the window-17 dense
+    schedule and the three-set schedule under both (dense is what the prover runs by default)."""
     import random
     import numpy as np
     import nzcb
@@ -152,12 +153,16 @@ def test_msm_2p21_witness_scalars_schedules_agree():
         # the Lagrange table's schedule (window 17, device-derived chunk, carry trees)
         sparse = _affine(eng.msm_fixed_dev(bases, n, sc, n, False, window=17, sparse=True))
         slo = _affine(eng.msm_fixed_dev(bases, h, sc, h, False, window=17, sparse=True))
-        # and the three-set schedule (the prover's A, B, C in one MSM): the same scalars as set 0
-        # and set 2, their halves' order reversed in set 1 (other buckets, same sizes)
+        # the same window under the dense schedule (fixed 48-entry chunk), the prover's default
+        dense17 = _affine(eng.msm_fixed_dev(bases, n, sc, n, False, window=17, sparse=False))
+        # and the three-set schedule (the prover's A, B, C in one MSM), dense (the default) and
+        # sparse (NZCB_SPARSE=1): the same scalars as set 0 and set 2, their halves' order
+        # reversed in set 1 (other buckets, same sizes)
         sc2 = nzcb.dev_alloc(n * 32)
         try:
             nzcb.h2d(sc2, raw[32 * h:] + raw[:32 * h])
-            s3 = [_affine(r) for r in eng.msm_sets_dev(bases, n, [sc, sc2, sc], n, False)]
+            s3 = {sp: [_affine(r) for r in eng.msm_sets_dev(bases, n, [sc, sc2, sc], n, False, sparse=sp)]
+                  for sp in (False, True)}
             rot = _affine(eng.msm_fixed_dev(bases, n, sc2, n, False, window=17, sparse=True))
         finally:
             nzcb.dev_free(sc2)
@@ -169,4 +174,6 @@ def test_msm_2p21_witness_scalars_schedules_agree():
     assert bn.g1_add(lo, hi) == fixed
     assert sparse == fixed
     assert bn.g1_add(slo, hi) == fixed
-    assert s3[0] == fixed and s3[2] == fixed and s3[1] == rot
+    assert dense17 == fixed
+    for sp in (False, True):
+        assert s3[sp][0] == fixed and s3[sp][2] == fixed and s3[sp][1] == rot, sp

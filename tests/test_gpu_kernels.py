@@ -2,6 +2,7 @@
 
 Bit-exact: every output is a unique field / affine-curve element.
 """
+import functools
 import os
 import random
 
@@ -82,15 +83,46 @@ def _affine(out):
     return None if x == 0 and y == 0 else (x, y)
 
 
-def _bases(n, seed):
+def _base_line(seed):
+    """First point P and step S of _bases(n, seed)."""
     rng = random.Random(seed)
-    pts = []
     p = bn.g1_mul(bn.G1_GEN, rng.randrange(1, R_MOD))
-    step = bn.g1_mul(bn.G1_GEN, rng.randrange(1, R_MOD))
+    return p, bn.g1_mul(bn.G1_GEN, rng.randrange(1, R_MOD))
+
+
+@functools.lru_cache(maxsize=None)
+def _bases(n, seed):
+    """The arithmetic progression P + i S, i < n. Cached (13000 points take seconds on the CPU)
+    and shared between tests: callers slice it and leave it unchanged."""
+    pts = []
+    p, step = _base_line(seed)
     for _ in range(n):
         pts.append(p)
         p = bn.g1_add(p, step)
     return pts
+
+
+@functools.lru_cache(maxsize=None)
+def _bases_lem(n, seed):
+    return b"".join(bn.g1_to_lem(p) for p in _bases(n, seed))
+
+
+def _msm_want(pts, seed, sc):
+    """Oracle MSM of sc over the first len(sc) points of pts = _bases(., seed). n equal scalars
+    v take the closed form v (n P + n (n - 1) / 2 S): two scalar multiplications instead of a
+    Pippenger run over thousands of points."""
+    n = len(sc)
+    if n == 0:
+        return None
+    if n > 1 and all(s == sc[0] for s in sc):
+        p, step = _base_line(seed)
+        return bn.g1_mul(bn.g1_add(bn.g1_mul(p, n), bn.g1_mul(step, n * (n - 1) // 2)), sc[0])
+    return bn.msm(pts[:n], sc)
+
+
+# the multi-piece cases' shared bases: one bucket of 13000 entries is 271 chunks of kChunk = 48,
+# more than one piece of kPieceCarries = 256 carries (msm.hip)
+_BIG_N, _BIG_SEED = 13000, 4243
 
 
 @pytest.mark.parametrize("n,kind", [(1, "rand"), (7, "rand"), (100, "rand"), (1000, "rand"), (3000, "rand"),
@@ -132,20 +164,23 @@ def test_msm_duplicate_and_negated_points(engine):
     assert got == want
 
 
-def _msm_fixed(engine, pts, sc, n_table=None, mont=False, window=0, sparse=False):
+def _msm_fixed(engine, pts, sc, n_table=None, mont=False, window=0, sparse=False, fold=False):
     """Fixed-base schedule (shifted-base table, one 2^19-bucket set) via device buffers;
-    window / sparse: another table window, the Lagrange table's sparse schedule."""
+    window / sparse: another table window, the Lagrange table's sparse schedule. fold: the
+    2^-256-folded table; sc are then the raw 256-bit integers the kernel buckets, uploaded as
+    they are in the place of Montgomery scalars."""
     import nzcb
     n = len(sc)
     n_table = n_table or n
     bases = b"".join(bn.g1_to_lem(p) for p in pts[:n_table])
-    scal = _lem(sc, R_MOD) if mont else b"".join(bn.to_le(s) for s in sc)
+    scal = _lem(sc, R_MOD) if mont and not fold else b"".join(bn.to_le(s) for s in sc)
     db, ds = nzcb.dev_alloc(len(bases)), nzcb.dev_alloc(max(len(scal), 32))
     try:
         nzcb.h2d(db, bases)
         if scal:
             nzcb.h2d(ds, scal)
-        return _affine(engine.msm_fixed_dev(db, n_table, ds, n, mont, window=window, sparse=sparse))
+        return _affine(engine.msm_fixed_dev(db, n_table, ds, n, mont or fold, window=window, sparse=sparse,
+                                            fold=fold))
     finally:
         nzcb.dev_free(db)
         nzcb.dev_free(ds)
@@ -200,14 +235,14 @@ def test_msm_fixed_base(engine, n, kind):
     assert _msm_fixed(engine, pts, sc, n_table=n + 5, mont=True) == want
 
 
-@pytest.mark.parametrize("n,kind", [(1, "rand"), (300, "rand"), (300, "zeros"), (3000, "ones"), (1500, "equal"),
-                                    (300, "rminus1"), (300, "top"), (3000, "witness"), (5000, "equal"),
-                                    (2000, "mixed"), (16, "equal"), (600, "half"), (3000, "negsmall")])
-def test_msm_sparse_schedule(engine, n, kind):
-    """The Lagrange table's schedule (round 6, msm.hip dyn_chunk): window 17, the accumulation
-    chunk derived on the device from the entry count (8 entries here), runs of more than four
-    carries through the log-depth piece and bucket trees. "ones" and "equal" put thousands of
-    entries into single buckets (1 to 3 pieces per bucket), "witness" is the A, B, C regime."""
+_W17_CASES = [(1, "rand"), (300, "rand"), (300, "zeros"), (3000, "ones"), (1500, "equal"),
+              (300, "rminus1"), (300, "top"), (3000, "witness"), (5000, "equal"),
+              (2000, "mixed"), (16, "equal"), (600, "half"), (3000, "negsmall")]
+
+
+@functools.lru_cache(maxsize=None)
+def _w17_case(n, kind):
+    """(bases, scalars, oracle result) of a window-17 case, computed once for both schedules."""
     rng = random.Random(4000 + n + len(kind))
     pts = _bases(n + 2, 2 * n + 3)
     if kind == "rand":
@@ -229,23 +264,56 @@ def test_msm_sparse_schedule(engine, n, kind):
         sc = _flip_kinds(kind, n, rng)
     if sc is None:
         sc = [rng.choice([0, 1, 2, R_MOD - 1, rng.randrange(R_MOD)]) for _ in range(n)]
-    want = bn.msm(pts[:n], sc)
-    assert _msm_fixed(engine, pts, sc, n_table=n + 2, window=17, sparse=True) == want
-    assert _msm_fixed(engine, pts, sc, n_table=n + 2, mont=True, window=17, sparse=True) == want
+    return pts, sc, _msm_want(pts, 2 * n + 3, sc)
 
 
-@pytest.mark.parametrize("n,kinds", [(1, ("rand", "ones", "zeros")), (300, ("witness", "equal", "rand")),
-                                     (3000, ("ones", "witness", "mixed")), (1500, ("equal", "equal", "ones")),
-                                     (700, ("zeros", "zeros", "witness")), (2000, ("witness", "rand")),
-                                     (1200, ("negsmall", "half", "negsmall"))])
-def test_msm_sets_schedule(engine, n, kinds):
-    """msm_enqueue_sets (round 6: the prover's A, B, C in one schedule over the Lagrange table):
-    each set's result equals its own MSM (oracle), for sets whose buckets collide in index
-    (equal scalars in two sets), empty sets, huge single buckets (ones, equal) and the
-    witness-like regime; Montgomery and normal-form scalars."""
-    import nzcb
+# the sparse cases keep the ids they had before the dense schedule joined them
+@pytest.mark.parametrize("n,kind,sparse", [pytest.param(n, k, sp, id=f"{n}-{k}" + ("" if sp else "-dense"))
+                                           for n, k in _W17_CASES for sp in (True, False)])
+def test_msm_sparse_schedule(engine, n, kind, sparse):
+    """Window 17 (the Lagrange table's), one set, under both schedules. sparse (round 6, msm.hip
+    dyn_chunk; NZCB_SPARSE=1): the accumulation chunk derived on the device from the entry count
+    (8 entries here), runs of more than four carries through the log-depth piece and bucket
+    trees. dense (the prover's default): the fixed chunk of 48, runs up to 17 carries in the
+    finalize's lanes, longer ones in pieces of 256. "ones" and "equal" put thousands of entries
+    into single buckets (sparse: 1 to 3 pieces per bucket; dense: 5000 equal scalars are one
+    piece of 105 carries), "witness" is the A, B, C regime."""
+    pts, sc, want = _w17_case(n, kind)
+    assert _msm_fixed(engine, pts, sc, n_table=n + 2, window=17, sparse=sparse) == want
+    assert _msm_fixed(engine, pts, sc, n_table=n + 2, mont=True, window=17, sparse=sparse) == want
+
+
+_SETS_CASES = [(1, ("rand", "ones", "zeros")), (300, ("witness", "equal", "rand")),
+               (3000, ("ones", "witness", "mixed")), (1500, ("equal", "equal", "ones")),
+               (700, ("zeros", "zeros", "witness")), (2000, ("witness", "rand")),
+               (1200, ("negsmall", "half", "negsmall"))]
+# the dense schedule's edges (msm.hip), all under the sparse one too
+_SETS_EDGES = (
+    # the bucketing tile edge, kTileScalars = 512: at 513 every set is two tiles (tps = 2, set =
+    # blockIdx.x / tps) and the second holds one scalar
+    [(n, ("rand", "witness", "mixed")) for n in (512, 513)]
+    # one bucket of n entries per window in every set, sets 0 and 2 the same vector: runs of
+    # 16 to 19 chunks of kChunk = 48 on both sides of kSeqSpan29 + 1 = 17 carries, the longest
+    # run a finalize lane sums before the bucket goes to the large list. A set's stream starts
+    # wherever the one before ended, so a bucket's start is not chunk-aligned and the sweep is
+    # what reaches both branches
+    + [(n, ("equal", "ones", "equal")) for n in (767, 768, 769, 815, 816, 817, 865)]
+    # 13000 entries in one bucket are 271 or 272 carries: two pieces of kPieceCarries = 256,
+    # which msm_large_final29_kernel<64> adds
+    + [(_BIG_N, ("ones", "equal", "zeros"))]
+    # no scalars at all: one infinity per set
+    + [(0, ("zeros", "zeros", "zeros"))]
+    # one and two sets in the schedule
+    + [(300, ("witness",)), (300, ("witness", "witness"))])
+
+
+@functools.lru_cache(maxsize=None)
+def _sets_case(n, kinds):
+    """(bases' seed, table size, scalar sets, oracle results) of a sets case, computed once for
+    both schedules."""
     rng = random.Random(5000 + n + len(kinds))
-    pts = _bases(n + 2, 3 * n + 11)
+    seed, nt = (_BIG_SEED, _BIG_N + 5) if n == _BIG_N else (3 * n + 11, n + 2)
+    pts = _bases(nt, seed)
 
     def scal(kind):
         if kind == "rand":
@@ -266,17 +334,39 @@ def test_msm_sets_schedule(engine, n, kinds):
     sets = [scal(k) for k in kinds]
     if kinds == ("equal", "equal", "ones"):
         sets[1] = list(sets[0])   # the same bucket in two sets
-    want = [bn.msm(pts[:n], sc) for sc in sets]
-    bases = b"".join(bn.g1_to_lem(p) for p in pts)
+    if kinds == ("equal", "ones", "equal"):
+        sets[2] = list(sets[0])
+    return seed, nt, sets, [_msm_want(pts, seed, sc) for sc in sets]
+
+
+# the sparse cases that predate the dense ones keep the ids they had
+@pytest.mark.parametrize("n,kinds,sparse",
+                         [pytest.param(n, k, sp, id=f"{n}-kinds{i}" + ("" if sp else "-dense"))
+                          for i, (n, k) in enumerate(_SETS_CASES) for sp in (True, False)] +
+                         [pytest.param(n, k, sp, id=f"{n}-{'_'.join(k)}-" + ("sparse" if sp else "dense"))
+                          for n, k in _SETS_EDGES for sp in (True, False)])
+def test_msm_sets_schedule(engine, n, kinds, sparse):
+    """msm_enqueue_sets (round 6: the prover's A, B, C in one schedule over the Lagrange table),
+    under the dense schedule the prover runs by default and the sparse one (NZCB_SPARSE=1):
+    each set's result equals its own MSM (oracle), for sets whose buckets collide in index
+    (equal scalars in two sets), empty sets, huge single buckets (ones, equal), the
+    witness-like regime and the edges of _SETS_EDGES; Montgomery and normal-form scalars."""
+    import nzcb
+    seed, nt, sets, want = _sets_case(n, kinds)
+    bases = _bases_lem(nt, seed)
     db = nzcb.dev_alloc(len(bases))
-    ds = [nzcb.dev_alloc(32 * n) for _ in sets]
+    ds = [nzcb.dev_alloc(max(32 * n, 32)) for _ in sets]
     try:
         nzcb.h2d(db, bases)
         for mont in (False, True):
             for d, sc in zip(ds, sets):
-                nzcb.h2d(d, _lem(sc, R_MOD) if mont else b"".join(bn.to_le(x) for x in sc))
-            got = [_affine(r) for r in engine.msm_sets_dev(db, n + 2, ds, n, mont)]
+                if sc:
+                    nzcb.h2d(d, _lem(sc, R_MOD) if mont else b"".join(bn.to_le(x) for x in sc))
+            raw = engine.msm_sets_dev(db, nt, ds, n, mont, sparse=sparse)
+            got = [_affine(r) for r in raw]
             assert got == want, (mont, [g == w for g, w in zip(got, want)])
+            if n == 0:
+                assert raw == [bytes(64)] * len(sets)
     finally:
         nzcb.dev_free(db)
         for d in ds:
@@ -309,6 +399,141 @@ def test_msm_long_carry_runs(engine, fixed):
         bases = b"".join(bn.g1_to_lem(p) for p in pts)
         got = _affine(engine.msm(bases, b"".join(bn.to_le(s) for s in sc), False))
         assert got == want
+
+
+@pytest.mark.parametrize("window", [0, 17])
+def test_msm_multi_piece_buckets(engine, window):
+    """The dense single-set schedule with 13000 equal scalars, on the default window and on
+    17: every window's bucket spans 271 or 272 chunks of kChunk = 48, more than one piece of
+    kPieceCarries = 256 carries, so msm_large_piece29_kernel cuts it in two and
+    msm_large_final29_kernel<64> adds the pieces (5000 scalars above are 105 carries, one
+    piece, which the final kernel only copies)."""
+    n = _BIG_N
+    pts = _bases(n + 5, _BIG_SEED)
+    sc = [random.Random(78 + window).randrange(R_MOD)] * n
+    want = _msm_want(pts, _BIG_SEED, sc)
+    assert _msm_fixed(engine, pts, sc, window=window) == want
+    assert _msm_fixed(engine, pts, sc, mont=True, window=window) == want
+
+
+@pytest.mark.parametrize("window", [0, 17])
+def test_msm_dense_large_list_grid_stride(engine, window):
+    """13000 scalars drawn in turn from ten values: ten buckets of 1300 entries (28 chunks, more
+    than kSeqSpan29 + 1) in each of the 13 or 15 windows, so the dense schedule's large list holds
+    130 or 149 buckets and as many pieces, more than the kLargePieceBlocks = kLargeFinalBlocks =
+    128 workgroups of msm_large_piece29_kernel and msm_large_final29_kernel<64>: some walk their
+    grid-stride loops twice. Oracle: sum_j v_j (m_j P + (j m_j + 10 m_j (m_j - 1) / 2) S) over
+    the residues j of the index mod 10, with m_j indices each."""
+    n, m = _BIG_N, 10
+    pts = _bases(n + 5, _BIG_SEED)
+    rng = random.Random(80 + window)
+    pool = [rng.randrange(R_MOD) for _ in range(m)]
+    sc = [pool[i % m] for i in range(n)]
+    p, step = _base_line(_BIG_SEED)
+    want = None
+    for j, v in enumerate(pool):
+        mj = len(range(j, n, m))
+        grp = bn.g1_add(bn.g1_mul(p, mj), bn.g1_mul(step, j * mj + m * mj * (mj - 1) // 2))
+        want = bn.g1_add(want, bn.g1_mul(grp, v))
+    assert _msm_fixed(engine, pts, sc, window=window) == want
+    assert _msm_fixed(engine, pts, sc, mont=True, window=window) == want
+
+
+def _fb_window():
+    """The PTau tables' window in this process (msm.hip fixed_base_window)."""
+    try:
+        c = int(os.environ.get("NZCB_FB_WINDOW", "20"))
+    except ValueError:
+        c = 20
+    return c if 16 <= c <= 20 else 20
+
+
+_KINV = pow(2, -256, R_MOD)
+
+
+def _folded_raw(kind, n, rng):
+    """Raw 256-bit integers (below r, as Montgomery forms are) for the folded table's digit pass
+    (msm.hip for_each_digit on the value as it stands: no from_mont, no scalar_min_form)."""
+    c = _fb_window()
+    nw = (255 + c - 1) // c
+    half, mask = 1 << (c - 1), (1 << c) - 1
+
+    def windows(f):  # digit f(w) in window w, cut to 253 bits (below r)
+        return sum(f(w) << (c * w) for w in range(nw)) & ((1 << 253) - 1)
+    if kind == "rand":
+        return [rng.randrange(R_MOD) for _ in range(n)]
+    if kind == "zeros":
+        return [0] * n
+    if kind == "ones":  # everything in bucket 0 of window 0
+        return [1] * n
+    if kind == "equal":
+        return [rng.randrange(R_MOD)] * n
+    if kind == "rminus1":
+        return [R_MOD - 1] * n
+    if kind == "witness":  # small values: mostly empty windows
+        return [rng.choice([0, 0, 1, 1, 2, rng.randrange(256), rng.randrange(1 << 17), rng.randrange(1 << 34),
+                            rng.randrange(R_MOD)]) for _ in range(n)]
+    if kind == "top":  # the top windows, and carry chains through every window ((1 << 253) - 1 and
+        # the all-MASK value: d = MASK + carry = 2^c, the `mag == 0` branch, no entry, carry on)
+        pool = [1 << 253, (1 << 253) - 1, (1 << 240) - 1, (1 << 239) * 3, (1 << c) * 5, R_MOD - 1,
+                R_MOD - (1 << 19), R_MOD - (1 << c), windows(lambda w: mask)]
+        return [rng.choice(pool) for _ in range(n)]
+    if kind == "half":  # digits at and around 2^(c-1), the sign switch, in every window
+        pool = [windows(lambda w: half), windows(lambda w: half + 1), windows(lambda w: half - 1),
+                windows(lambda w: half + (w & 1)), windows(lambda w: half - 1 + (w & 1)),
+                windows(lambda w: half if w % 3 else mask), windows(lambda w: rng.choice([half, half + 1, mask, 0]))]
+        return [rng.choice(pool + [windows(lambda w: rng.choice([half - 1, half, half + 1, mask, 0, 1]))])
+                for _ in range(n)]
+    return [rng.choice([0, 1, 2, R_MOD - 1, rng.randrange(R_MOD)]) for _ in range(n)]
+
+
+@pytest.mark.parametrize("n,kind", [(1, "rand"), (100, "rand"), (2000, "rand"), (300, "zeros"), (300, "ones"),
+                                    (300, "equal"), (300, "rminus1"), (300, "mixed"), (1500, "witness"),
+                                    (600, "top"), (600, "half")])
+def test_msm_fixed_base_folded(engine, n, kind):
+    """The prover's PTau table (MsmBaseTable::mont_folded, msm_table_kernel's double-and-add by
+    2^-256 mod r): the digits come from the uploaded 256-bit integer v as it stands, and the
+    result is sum (v_i 2^-256 mod r) B_i. Table over more bases than the MSM uses."""
+    rng = random.Random(7000 + n + len(kind))
+    seed = 5 * n + 7
+    pts = _bases(n + 5, seed)
+    raw = _folded_raw(kind, n, rng)
+    want = _msm_want(pts, seed, [v * _KINV % R_MOD for v in raw])
+    assert _msm_fixed(engine, pts, raw, n_table=n + 5, fold=True) == want
+
+
+def test_msm_fixed_base_folded_infinity_bases(engine):
+    """Infinity bases (every row of the folded table is infinity too), a duplicated and a
+    negated base."""
+    g = bn.g1_mul(bn.G1_GEN, 778)
+    pts = [g, None, bn.g1_neg(g), g, None, g]
+    raw = [5, 6, 5, 7 << 200, 9, R_MOD - 5]
+    assert _msm_fixed(engine, pts, raw, fold=True) == bn.msm(pts, [v * _KINV % R_MOD for v in raw])
+
+
+def test_msm_fixed_base_folded_needs_montgomery(engine):
+    """A folded table with normal-form scalars is refused (msm_enqueue_impl)."""
+    import nzcb
+    db, ds = nzcb.dev_alloc(64 * 4), nzcb.dev_alloc(32 * 4)
+    try:
+        nzcb.h2d(db, _bases_lem(4, 99))
+        nzcb.h2d(ds, b"".join(bn.to_le(s) for s in (1, 2, 3, 4)))
+        with pytest.raises(nzcb.NzcbError) as ei:
+            engine.msm_fixed_dev(db, 4, ds, 4, False, fold=True)
+        assert ei.value.code == 1 and ei.value.name == "ARG"   # NZCB_ERR_ARG
+    finally:
+        nzcb.dev_free(db)
+        nzcb.dev_free(ds)
+
+
+def test_msm_folded_table_multi_piece(engine):
+    """13000 equal raw values over the folded table on the default window: the multi-piece
+    buckets of test_msm_multi_piece_buckets on the table the prover's dense commitments use."""
+    n = _BIG_N
+    pts = _bases(n + 5, _BIG_SEED)
+    v = random.Random(79).randrange(R_MOD)
+    want = _msm_want(pts, _BIG_SEED, [v * _KINV % R_MOD] * n)
+    assert _msm_fixed(engine, pts, [v] * n, fold=True) == want
 
 
 @pytest.mark.parametrize("kind", ["rand", "equal", "mixed", "small"])
