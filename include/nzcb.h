@@ -210,6 +210,27 @@ int nzcb_vk_to_json(const uint8_t* vk, char* out, size_t cap);
  * signals (n_public x 32 B LE), else 0. transcript_public as nzcb_ctx_set_transcript_public. */
 int nzcb_verify(const uint8_t* vk, const uint8_t* proof, const uint8_t* pub, int n_public, int transcript_public,
                 int* valid, nzcb_err* err);
+/* nzcb_verify for `count` proofs of one key at once: one pairing check for the whole batch
+ * instead of one per proof, and the 20 G1 scalar multiplications of every proof on GPU
+ * `device` (own stream and buffers per call, no nzcb_ctx needed; may run while a context
+ * proves on the same device). device = NZCB_VERIFY_HOST runs the same algorithm with the
+ * scalar multiplications on the host, so the library still verifies without a GPU.
+ *   proofs : count x NZCB_PROOF_BYTES;  pubs : item i at pubs + i * pub_stride
+ *   (pub_stride >= 32 * n_public);  valid_out : count ints.
+ * Returns 0 when the batch was examined, whatever the verdicts (count = 0 is fine).
+ * valid_out[i] is what nzcb_verify says of item i, up to the soundness error of the random
+ * weights: the items are combined under independent 128-bit weights rho_i, so a batch holding
+ * an invalid item passes a combined check with probability of order 2^-128; a failing check is
+ * bisected (at most 1 + 2 k ceil(log2 N) pairing checks for k invalid among N well-formed items).
+ * seed = NULL draws the weights from the OS CSPRNG, like the blinding. A 32-byte seed makes
+ * rho_i the low 128 bits of keccak256(seed || LE32(i)) (the digest read as a big-endian
+ * integer; zero becomes 1): FOR REPRODUCIBLE TESTS ONLY, since whoever knows the weights
+ * before choosing the proofs can make invalid items cancel. */
+#define NZCB_VERIFY_HOST (-1)
+int nzcb_verify_batch(const uint8_t* vk, const uint8_t* proofs /* count x NZCB_PROOF_BYTES */,
+                      const uint8_t* pubs, size_t pub_stride, int n_public, int count,
+                      int transcript_public, int device /* >= 0, or NZCB_VERIFY_HOST */,
+                      const uint8_t* seed /* 32 B or NULL */, int* valid_out /* count */, nzcb_err* err);
 /* snarkjs `zkey export soliditycalldata` for PLONK (/root/reference/Makefile:57,62 verifier):
  * "0x<proof hex>,[\"0x<pub>\",...]"; returns 0, or the needed size if cap is short. */
 int nzcb_proof_to_calldata(const uint8_t* proof, const uint8_t* pub, int n_public, char* out, size_t cap);

@@ -134,6 +134,29 @@ int nzcb_engine_time_msm2(nzcb_engine* e, const void* bases, const void* scalars
 int nzcb_engine_fr_mul(nzcb_engine* e, const uint8_t* a_lem, const uint8_t* b_lem, uint8_t* out_lem, size_t n,
                        int field_q, nzcb_err* err);
 
+/* ---- Batch verification (csrc/verify_batch.hip) -------------------------------------- */
+/* Weighted sums of G1 points in groups, on GPU `device` or on the host (NZCB_VERIFY_HOST; the
+ * same functions compiled for the host, byte-equal results). Needs no engine or context: own
+ * stream and buffers per call. points: n x 64 B (x || y, 32-byte LE normal form, zeros =
+ * infinity); scalars: n x 32 B LE normal form, < r; group_end: `groups` exclusive ends,
+ * non-decreasing, n = the last one (<= 2^24); out: groups x 64 B, group g = the sum of
+ * scalars[i] * points[i] over group_end[g - 1] <= i < group_end[g], in the points' format. */
+int nzcb_engine_g1_lincomb(int device, const uint8_t* points, const uint8_t* scalars, const uint32_t* group_end,
+                           size_t groups, uint8_t* out, nzcb_err* err);
+/* nzcb_verify_batch (nzcb.h) with its intermediate results. points_out (may be NULL): count x
+ * 128 B, L'_i || R'_i = rho_i L_i || rho_i R_i (the two pairing inputs of item i under its
+ * weight), zeros for items rejected before the sums (malformed, off-curve, wrong n_public).
+ * pairing_checks (may be NULL): how many pairing checks the call ran. */
+int nzcb_engine_verify_batch(const uint8_t* vk, const uint8_t* proofs, const uint8_t* pubs, size_t pub_stride,
+                             int n_public, int count, int transcript_public, int device, const uint8_t* seed,
+                             int* valid_out, uint8_t* points_out, int* pairing_checks, nzcb_err* err);
+/* Milliseconds of the calling thread's last nzcb_(engine_)verify_batch: [0] host parsing,
+ * challenges and weighted scalars, [1] the group sums (wall, with copies), [2] the scalar-
+ * multiplication kernel and [3] the group-sum kernel (HIP events; 0 on the host path),
+ * [4] the pairing checks with their host sums, [5] the number of pairing checks. Returns the
+ * number of values written (cap <= 6). */
+int nzcb_debug_verify_batch_timings(double* ms, int cap);
+
 #ifdef __cplusplus
 }
 #endif

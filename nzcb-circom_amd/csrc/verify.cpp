@@ -29,6 +29,7 @@
 #include "msm.h"
 #include "ntt.h"
 #include "transcript.h"
+#include "verify.h"
 #include "zkey.h"
 
 namespace nzcb {
@@ -46,10 +47,7 @@ Fq fq_from_normal(const uint32_t (&v)[8]) {
   return to_mont(x);
 }
 
-// ---------------------------------------------------------------- Fq2 = Fq[u]/(u^2+1)
-struct F2 {
-  Fq a, b;
-};
+// ---------------------------------------------------------------- Fq2 = Fq[u]/(u^2+1) (F2: verify.h)
 F2 f2_add(const F2& x, const F2& y) { return {x.a + y.a, x.b + y.b}; }
 F2 f2_sub(const F2& x, const F2& y) { return {x.a - y.a, x.b - y.b}; }
 F2 f2_neg(const F2& x) { return {neg(x.a), neg(x.b)}; }
@@ -143,11 +141,7 @@ F12 f12_pow(F12 a, const uint64_t* e, int nlimbs) {
   return r;
 }
 
-// ---------------------------------------------------------------- G2 (twist), affine
-struct P2 {
-  F2 x, y;
-  bool inf = false;
-};
+// ---------------------------------------------------------------- G2 (twist), affine (P2: verify.h)
 P2 p2_add(const P2& t, const P2& s) {
   if (t.inf) return s;
   if (s.inf) return t;
@@ -226,11 +220,15 @@ F12 miller_loop(const P2& q, const G1Affine& p) {
   return f;
 }
 
+}  // namespace
+
 bool pairing_check(const std::vector<std::pair<G1Affine, P2>>& pairs) {
   F12 f = f12_one();
   for (const auto& pq : pairs) f = f12_mul(f, miller_loop(pq.second, pq.first));
   return f12_eq(f12_pow(f, kFinalExp, 44), f12_one());
 }
+
+namespace {
 
 // ---------------------------------------------------------------- G1 helpers (host)
 G1xyzz g1_mul(const G1Affine& p, const Fr& k_mont) {
@@ -243,11 +241,16 @@ G1xyzz g1_mul(const G1Affine& p, const Fr& k_mont) {
   }
   return acc;
 }
+}  // namespace
+
 G1Affine g1_neg(const G1Affine& p) {
   G1Affine r = p;
   if (!p.is_inf()) r.y = neg(p.y);
   return r;
 }
+
+namespace {
+
 bool g1_on_curve(const G1Affine& p) {
   if (p.is_inf()) return true;
   return p.y * p.y == p.x * p.x * p.x + fq_small(3);
@@ -267,6 +270,8 @@ Fr fr_from_le_checked(const uint8_t* le, bool* ok) {
   if (!(y == x)) *ok = false;  // >= r
   return to_mont(x);
 }
+}  // namespace
+
 G1Affine g1_from_le(const uint8_t* p, bool* ok) {
   G1Affine a;
   a.x = fq_from_le_normal(p, ok);
@@ -283,14 +288,9 @@ void g1_to_le(const G1Affine& a, uint8_t* out) {
   std::memcpy(out + 32, y.v, 32);
 }
 
-// binary verification key (include/nzcb.h NZCB_VK_BYTES)
-struct Vk {
-  uint32_t nPublic = 0, power = 0;
-  Fr k1, k2, w;
-  G1Affine q[8];  // Qm, Ql, Qr, Qo, Qc, S1, S2, S3
-  P2 x2;
-};
+namespace {
 
+// binary verification key (include/nzcb.h NZCB_VK_BYTES; Vk: verify.h)
 void vk_write(const Zkey& z, uint8_t* out) {
   std::memcpy(out, &z.nPublic, 4);
   const uint32_t pw = (uint32_t)z.power;
@@ -307,6 +307,8 @@ void vk_write(const Zkey& z, uint8_t* out) {
   }
   fr_to_le_normal(fr_root_of_unity(z.power), out + 712);
 }
+
+}  // namespace
 
 Vk vk_read(const uint8_t* in, bool* ok) {
   Vk v;
@@ -335,24 +337,28 @@ P2 g2_generator() {
   return g;
 }
 
-}  // namespace
-
-// snarkjs plonk_verify restated (see the header comment); true = valid
-bool plonk_verify(const Vk& vk, const uint8_t* proof, const uint8_t* pub, int npub, bool transcript_public) {
+// step (a): canonical encodings, nPublic, points on the curve
+bool plonk_parse(const Vk& vk, const uint8_t* proof, const uint8_t* pub, int npub, ProofParsed* out) {
   bool ok = true;
-  G1Affine pt[9];  // A, B, C, Z, T1, T2, T3, Wxi, Wxiw
-  for (int i = 0; i < 9; i++) pt[i] = g1_from_le(proof + 64 * i, &ok);
-  Fr ev[7];  // eval_a, eval_b, eval_c, eval_s1, eval_s2, eval_zw, eval_r
-  for (int i = 0; i < 7; i++) ev[i] = fr_from_le_checked(proof + 576 + 32 * i, &ok);
-  std::vector<Fr> pubs(npub);
-  for (int i = 0; i < npub; i++) pubs[i] = fr_from_le_checked(pub + 32 * i, &ok);
+  for (int i = 0; i < 9; i++) out->pt[i] = g1_from_le(proof + 64 * i, &ok);
+  for (int i = 0; i < 7; i++) out->ev[i] = fr_from_le_checked(proof + 576 + 32 * i, &ok);
+  out->pubs.resize(npub);
+  for (int i = 0; i < npub; i++) out->pubs[i] = fr_from_le_checked(pub + 32 * i, &ok);
   if (!ok || (uint32_t)npub != vk.nPublic) return false;
-  for (const auto& p : pt)
+  for (const auto& p : out->pt)
     if (!g1_on_curve(p)) return false;
+  return true;
+}
+
+// step (b): challenges (transcript.h, as the prover) and the terms of the two pairing inputs
+void plonk_terms(const Vk& vk, const ProofParsed& pp, bool transcript_public, VerifyTerms* out) {
+  const G1Affine* pt = pp.pt;
+  const Fr* ev = pp.ev;
+  const std::vector<Fr>& pubs = pp.pubs;
+  const int npub = (int)pubs.size();
   const G1Affine &A = pt[0], &B = pt[1], &C = pt[2], &Z = pt[3], &T1 = pt[4], &T2 = pt[5], &T3 = pt[6],
                  &Wxi = pt[7], &Wxiw = pt[8];
   const Fr &ea = ev[0], &eb = ev[1], &ec = ev[2], &es1 = ev[3], &es2 = ev[4], &ezw = ev[5], &er = ev[6];
-  // challenges (transcript.h, as the prover)
   std::vector<uint8_t> tr;
   auto put_fr = [&](const Fr& x) {
     uint8_t b[32];
@@ -382,7 +388,7 @@ bool plonk_verify(const Vk& vk, const uint8_t* proof, const uint8_t* pub, int np
   put_g1(T3);
   const Fr xi = hash_to_fr(tr);
   tr.clear();
-  for (const auto& e : ev) put_fr(e);
+  for (int i = 0; i < 7; i++) put_fr(ev[i]);
   Fr v[7];
   v[1] = hash_to_fr(tr);
   for (int i = 2; i <= 6; i++) v[i] = v[i - 1] * v[1];
@@ -419,19 +425,36 @@ bool plonk_verify(const Vk& vk, const uint8_t* proof, const uint8_t* pub, int np
   // D, F, E and the two pairing inputs
   const G1Affine &Qm = vk.q[0], &Ql = vk.q[1], &Qr = vk.q[2], &Qo = vk.q[3], &Qc = vk.q[4], &S1 = vk.q[5],
                  &S2 = vk.q[6], &S3 = vk.q[7];
-  std::vector<std::pair<const G1Affine*, Fr>> terms = {
-      {&Qm, ea * eb * v[1]}, {&Ql, ea * v[1]}, {&Qr, eb * v[1]}, {&Qo, ec * v[1]}, {&Qc, v[1]},
-      {&Z, (e2 + e4) * v[1] + u}, {&S3, neg(e3 * v[1])},
-      {&T1, one}, {&T2, xin}, {&T3, xin * xin}, {&A, v[2]}, {&B, v[3]}, {&C, v[4]}, {&S1, v[5]}, {&S2, v[6]},
-      {&Wxi, xi}, {&Wxiw, u * xi * vk.w}};
-  G1xyzz rhs = G1xyzz::inf();
-  for (const auto& tm : terms) rhs = xyzz_add(rhs, g1_mul(*tm.first, tm.second));
   const Fr e = t + v[1] * er + v[2] * ea + v[3] * eb + v[4] * ec + v[5] * es1 + v[6] * es2 + u * ezw;
   G1Affine gen;
   gen.x = fq_small(1);
   gen.y = fq_small(2);
-  rhs = xyzz_add(rhs, g1_mul(g1_neg(gen), e));
-  const G1xyzz lhs = xyzz_add(g1_mul(Wxi, one), g1_mul(Wxiw, u));
+  const std::pair<const G1Affine*, Fr> terms[kVerifyRTerms] = {
+      {&Qm, ea * eb * v[1]}, {&Ql, ea * v[1]}, {&Qr, eb * v[1]}, {&Qo, ec * v[1]}, {&Qc, v[1]},
+      {&Z, (e2 + e4) * v[1] + u}, {&S3, neg(e3 * v[1])},
+      {&T1, one}, {&T2, xin}, {&T3, xin * xin}, {&A, v[2]}, {&B, v[3]}, {&C, v[4]}, {&S1, v[5]}, {&S2, v[6]},
+      {&Wxi, xi}, {&Wxiw, u * xi * vk.w}, {&gen, neg(e)}};
+  for (int i = 0; i < kVerifyRTerms; i++) {
+    out->rp[i] = *terms[i].first;
+    out->rs[i] = terms[i].second;
+  }
+  out->lp[0] = Wxi;
+  out->ls[0] = one;
+  out->lp[1] = Wxiw;
+  out->ls[1] = u;
+}
+
+// snarkjs plonk_verify restated (see the header comment); true = valid
+bool plonk_verify(const Vk& vk, const uint8_t* proof, const uint8_t* pub, int npub, bool transcript_public) {
+  ProofParsed pp;
+  if (!plonk_parse(vk, proof, pub, npub, &pp)) return false;
+  VerifyTerms tm;
+  plonk_terms(vk, pp, transcript_public, &tm);
+  // step (c)
+  G1xyzz rhs = G1xyzz::inf();
+  for (int i = 0; i < kVerifyRTerms; i++) rhs = xyzz_add(rhs, g1_mul(tm.rp[i], tm.rs[i]));
+  G1xyzz lhs = G1xyzz::inf();
+  for (int i = 0; i < kVerifyLTerms; i++) lhs = xyzz_add(lhs, g1_mul(tm.lp[i], tm.ls[i]));
   std::vector<std::pair<G1Affine, P2>> pairs = {{g1_neg(xyzz_to_affine(lhs)), vk.x2},
                                                 {xyzz_to_affine(rhs), g2_generator()}};
   return pairing_check(pairs);

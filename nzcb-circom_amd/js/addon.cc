@@ -612,6 +612,86 @@ napi_value Verify(napi_env env, napi_callback_info info) {
   return r;
 }
 
+// one verifyBatch call: nzcb_verify_batch on a worker thread (async work), the promise
+// settled on the main thread; the inputs are copied, so the caller's Buffers may change
+struct VerifyBatchWork {
+  napi_deferred deferred = nullptr;
+  napi_async_work work = nullptr;
+  std::vector<uint8_t> vk, proofs, pubs;
+  int n_public = 0, count = 0, device = 0;
+  bool tp = true;
+  std::vector<int> valid;
+  int rc = 0;
+  nzcb_err err{};
+};
+
+void verify_batch_execute(napi_env, void* data) {
+  VerifyBatchWork* w = static_cast<VerifyBatchWork*>(data);
+  w->rc = nzcb_verify_batch(w->vk.data(), w->proofs.data(), w->pubs.data(), 32 * (size_t)w->n_public, w->n_public,
+                            w->count, w->tp ? 1 : 0, w->device, nullptr, w->valid.data(), &w->err);
+}
+
+void verify_batch_complete(napi_env env, napi_status status, void* data) {
+  VerifyBatchWork* w = static_cast<VerifyBatchWork*>(data);
+  if (status != napi_ok || w->rc != 0) {
+    napi_reject_deferred(env, w->deferred,
+                         make_error(env, w->rc ? w->err.code : NZCB_ERR_INTERNAL,
+                                    w->rc ? w->err.msg : "verifyBatch: the work was cancelled"));
+  } else {
+    napi_value arr;
+    napi_create_array_with_length(env, (size_t)w->count, &arr);
+    for (int i = 0; i < w->count; i++) {
+      napi_value b;
+      napi_get_boolean(env, w->valid[i] != 0, &b);
+      napi_set_element(env, arr, (uint32_t)i, b);
+    }
+    napi_resolve_deferred(env, w->deferred, arr);
+  }
+  napi_delete_async_work(env, w->work);
+  delete w;
+}
+
+// verifyBatch(vk: Buffer, proofs: Buffer (count x NZCB_PROOF_BYTES), pubs: Buffer (count x
+// nPublic x 32), count: number, transcriptPublic: bool, device: number) -> Promise<boolean[]>
+napi_value VerifyBatch(napi_env env, napi_callback_info info) {
+  size_t argc = 6;
+  napi_value argv[6];
+  CHECK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  const uint8_t *vk, *proofs, *pubs;
+  size_t vl, pl, ul;
+  int32_t count = 0, device = 0;
+  bool tp = true;
+  if (argc < 4 || !buf_arg(env, argv[0], &vk, &vl) || !buf_arg(env, argv[1], &proofs, &pl) ||
+      !buf_arg(env, argv[2], &pubs, &ul) || napi_get_value_int32(env, argv[3], &count) != napi_ok || count < 0 ||
+      vl != NZCB_VK_BYTES || pl != (size_t)count * NZCB_PROOF_BYTES || (count ? ul % (32 * (size_t)count) : ul)) {
+    napi_throw_type_error(env, nullptr,
+                          "verifyBatch(vk: Buffer, proofs: Buffer, pubs: Buffer, count, transcriptPublic, device)");
+    return nullptr;
+  }
+  if (argc > 4) napi_get_value_bool(env, argv[4], &tp);
+  if (argc > 5) napi_get_value_int32(env, argv[5], &device);
+  VerifyBatchWork* w = new VerifyBatchWork();
+  w->vk.assign(vk, vk + vl);
+  w->proofs.assign(proofs, proofs + pl);
+  w->pubs.assign(pubs, pubs + ul);
+  w->count = count;
+  w->n_public = count ? (int)(ul / 32 / (size_t)count) : 0;
+  w->device = device;
+  w->tp = tp;
+  w->valid.assign((size_t)count + 1, 0);
+  napi_value promise, name;
+  if (napi_create_promise(env, &w->deferred, &promise) != napi_ok ||
+      napi_create_string_utf8(env, "nzcb.verifyBatch", NAPI_AUTO_LENGTH, &name) != napi_ok ||
+      napi_create_async_work(env, nullptr, name, verify_batch_execute, verify_batch_complete, w, &w->work) !=
+          napi_ok ||
+      napi_queue_async_work(env, w->work) != napi_ok) {
+    delete w;
+    napi_throw_error(env, nullptr, "nzcb addon: N-API call failed");
+    return nullptr;
+  }
+  return promise;
+}
+
 // calldata(proof: Buffer, pub: Buffer) -> string (snarkjs `zkey export soliditycalldata`)
 napi_value Calldata(napi_env env, napi_callback_info info) {
   size_t argc = 2;
@@ -736,6 +816,7 @@ napi_value Init(napi_env env, napi_value exports) {
       {"remapWitnessProgram", nullptr, RemapWitnessProgram, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"vkToJson", nullptr, VkToJson, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"verify", nullptr, Verify, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"verifyBatch", nullptr, VerifyBatch, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"calldata", nullptr, Calldata, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"vkToSolidity", nullptr, VkToSolidity, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"nzcpWitness", nullptr, NzcpWitness, nullptr, nullptr, nullptr, napi_default, nullptr},

@@ -447,6 +447,27 @@ async function verify(vkVerifier, publicSignals, proof, logger, options) {
   return ok;
 }
 
+// plonk.verify for many proofs of one key (include/nzcb.h nzcb_verify_batch): one pairing
+// check for the batch and the G1 scalar multiplications on the GPU, on a worker thread (the
+// event loop is not blocked). options: {device (default 0; -1 = on the host), transcriptPublic}.
+// Resolves to one boolean per proof.
+async function verifyBatch(vkVerifier, publicSignalsArray, proofArray, logger, options) {
+  options = options || {};
+  const tp = options.transcriptPublic === undefined ? true : !!options.transcriptPublic;
+  const count = proofArray.length;
+  if (publicSignalsArray.length !== count) throw new Error('verifyBatch: one publicSignals array per proof');
+  const nPublic = count ? publicSignalsArray[0].length : 0;
+  if (publicSignalsArray.some((p) => p.length !== nPublic)) {
+    throw new Error('verifyBatch: every item has the same number of public signals');
+  }
+  const ok = await addon.verifyBatch(vkBuf(vkVerifier), Buffer.concat(proofArray.map(proofBuf).concat([Buffer.alloc(0)])),
+    Buffer.concat(publicSignalsArray.map(pubBuf).concat([Buffer.alloc(0)])), count, tp,
+    options.device === undefined ? 0 : options.device);
+  const log = loggerFn(logger);
+  if (log) log(`verifyBatch: ${ok.filter((x) => x).length} of ${count} valid`);
+  return ok;
+}
+
 async function exportSolidityCallData(proof, publicSignals) {
   return addon.calldata(proofBuf(proof), pubBuf(publicSignals));
 }
@@ -503,7 +524,7 @@ function nzcpWitness(inputs, options) {
 }
 
 module.exports = {
-  plonk: { setup, prove, fullProve, verify, exportSolidityCallData },
+  plonk: { setup, prove, fullProve, verify, verifyBatch, exportSolidityCallData },
   zKey: { exportVerificationKey, exportSolidityVerifier },
   nzcp: Object.assign({}, require('./nzcp.js'), { witness: nzcpWitness }),
   wtns: { calculate: wtnsCalculate, remapProgram },

@@ -46,11 +46,13 @@ EXPORTED_SYMBOLS = [
     "nzcb_plonk_setup", "nzcb_prove_batch_status", "nzcb_wprog_remap", "nzcb_prove_logged", "nzcb_memcpy_d2d_async",
     "nzcb_debug_guard_check", "nzcb_debug_guard_selftest", "nzcb_debug_inject_fault", "nzcb_debug_f29",
     "nzcb_msm_table_create_lagrange",
+    "nzcb_verify_batch", "nzcb_engine_g1_lincomb", "nzcb_engine_verify_batch", "nzcb_debug_verify_batch_timings",
 ]
 
 NZCB_FAULT_QUOTIENT = 1  # include/nzcb_internal.h
 NZCB_DEBUG_GENERIC_K = 2  # include/nzcb_internal.h
 NZCB_FAULT_LANE_ALLOC = 3  # include/nzcb_internal.h
+VERIFY_HOST = -1  # include/nzcb.h NZCB_VERIFY_HOST: verify_batch with the scalar multiplications on the host
 
 
 def lagrange_commit_enabled() -> bool:
@@ -239,6 +241,12 @@ def load(path: str | None = None):
         "nzcb_debug_guard_selftest": (c_int, [c_int, POINTER(_Err)]),
         "nzcb_debug_inject_fault": (c_int, [c_void_p, c_int]),
         "nzcb_debug_f29": (c_int, [c_int, c_int, POINTER(c_uint32), c_size_t, POINTER(c_uint32), POINTER(_Err)]),
+        "nzcb_verify_batch": (c_int, [u8p, u8p, u8p, c_size_t, c_int, c_int, c_int, c_int, u8p, POINTER(c_int),
+                                      POINTER(_Err)]),
+        "nzcb_engine_g1_lincomb": (c_int, [c_int, u8p, u8p, POINTER(c_uint32), c_size_t, u8p, POINTER(_Err)]),
+        "nzcb_engine_verify_batch": (c_int, [u8p, u8p, u8p, c_size_t, c_int, c_int, c_int, c_int, u8p, POINTER(c_int),
+                                             u8p, POINTER(c_int), POINTER(_Err)]),
+        "nzcb_debug_verify_batch_timings": (c_int, [POINTER(c_double), c_int]),
     }
     lib.missing_symbols = []
     for name, (res, args) in sigs.items():
@@ -441,6 +449,52 @@ class Engine:
         _check(self.lib.nzcb_engine_msm_dev(self.h, dev_bases, dev_scalars, n, int(scalars_mont), out,
                                             ctypes.byref(err)), err)
         return bytes(out)
+
+    # The batch verifier's entries (include/nzcb_internal.h) take a device, not an engine.
+    @staticmethod
+    def g1_lincomb(points: bytes, scalars: bytes, group_end, device: int = 0) -> list:
+        """Per group the sum of scalars[i] * points[i] (nzcb_engine_g1_lincomb): points n x 64 B
+        affine LE normal form (zeros = infinity), scalars n x 32 B LE, group_end the groups'
+        exclusive ends; device = VERIFY_HOST runs the host path. Returns one 64-byte point per group."""
+        groups = len(group_end)
+        n = group_end[-1] if groups else 0
+        assert len(points) == 64 * n and len(scalars) == 32 * n
+        ends = (c_uint32 * max(groups, 1))(*group_end)
+        out = _out(64 * groups)
+        err = _Err()
+        _check(load().nzcb_engine_g1_lincomb(device, _buf(points), _buf(scalars), ends, groups, out,
+                                             ctypes.byref(err)), err)
+        return [bytes(out)[64 * g:64 * g + 64] for g in range(groups)]
+
+    @staticmethod
+    def verify_batch(vk: bytes, proofs, publics, transcript_public: bool = True, device: int = 0,
+                     seed: bytes | None = None, n_public: int | None = None):
+        """nzcb_engine_verify_batch: (verdicts, per-item L' || R' points (128 B each, zeros for
+        items rejected before the sums), number of pairing checks)."""
+        count = len(proofs)
+        assert len(publics) == count and all(len(p) == PROOF_BYTES for p in proofs)
+        if n_public is None:
+            n_public = len(publics[0]) // 32 if count else 0
+        stride = max([32 * n_public] + [len(p) for p in publics])
+        pubs = b"".join(bytes(p).ljust(stride, b"\0") for p in publics)
+        assert seed is None or len(seed) == 32
+        valid = (c_int * max(count, 1))()
+        pts = _out(128 * count)
+        checks = c_int(0)
+        err = _Err()
+        _check(load().nzcb_engine_verify_batch(_buf(vk), _buf(b"".join(proofs)), _buf(pubs), stride, n_public, count,
+                                               int(transcript_public), device, _buf(seed) if seed else None, valid,
+                                               pts, ctypes.byref(checks), ctypes.byref(err)), err)
+        raw = bytes(pts)
+        return ([bool(valid[i]) for i in range(count)], [raw[128 * i:128 * i + 128] for i in range(count)],
+                checks.value)
+
+    @staticmethod
+    def verify_batch_timings() -> list:
+        """Milliseconds of this thread's last verify_batch (nzcb_debug_verify_batch_timings)."""
+        ms = (c_double * 6)()
+        k = load().nzcb_debug_verify_batch_timings(ms, 6)
+        return list(ms)[:k]
 
 
 def dev_alloc(nbytes: int) -> int:
@@ -979,6 +1033,28 @@ def verify(vk: bytes, proof: bytes, public: bytes, transcript_public: bool = Tru
     return bool(valid.value)
 
 
+def verify_batch(vk: bytes, proofs, publics, transcript_public: bool = True, device: int = 0,
+                 seed: bytes | None = None) -> list:
+    """nzcb.verify for many proofs of one key (include/nzcb.h nzcb_verify_batch): one pairing
+    check for the batch, the G1 scalar multiplications on GPU `device` (VERIFY_HOST: on the
+    host). proofs: binary proofs; publics: per proof nPublic x 32-byte LE. `seed` (32 bytes)
+    fixes the random weights, for reproducible tests only. Returns one bool per proof."""
+    count = len(proofs)
+    if len(publics) != count or any(len(p) != PROOF_BYTES for p in proofs):
+        raise ValueError("verify_batch: one public-signal buffer per proof of PROOF_BYTES bytes")
+    if seed is not None and len(seed) != 32:
+        raise ValueError("verify_batch: the seed is 32 bytes")
+    n_public = len(publics[0]) // 32 if count else 0
+    if any(len(p) != 32 * n_public for p in publics):
+        raise ValueError("verify_batch: every item has the same number of public signals")
+    valid = (c_int * max(count, 1))()
+    err = _Err()
+    _check(load().nzcb_verify_batch(_buf(vk), _buf(b"".join(proofs)), _buf(b"".join(publics)), 32 * n_public,
+                                    n_public, count, int(transcript_public), device,
+                                    _buf(seed) if seed else None, valid, ctypes.byref(err)), err)
+    return [bool(valid[i]) for i in range(count)]
+
+
 def proof_to_calldata(proof: bytes, public: bytes) -> str:
     """snarkjs `zkey export soliditycalldata` text for a PLONK proof."""
     return _json_text(load().nzcb_proof_to_calldata, _buf(proof), _buf(public), len(public) // 32)
@@ -1006,6 +1082,14 @@ class plonk:
         """snarkjs.plonk.verify(vkey, publicSignals, proof) on the JSON objects."""
         pub = b"".join(_le(x) for x in publicSignals)
         return verify(vk_from_json(vk_verifier), proof_from_json(proof), pub, transcript_public)
+
+    @staticmethod
+    def verify_batch(vk_verifier: dict, publicSignalsArray, proofArray, transcript_public: bool = True,
+                     device: int = 0) -> list:
+        """plonk.verify for many proofs of one key on the JSON objects: one bool per proof."""
+        pubs = [b"".join(_le(x) for x in ps) for ps in publicSignalsArray]
+        return verify_batch(vk_from_json(vk_verifier), [proof_from_json(p) for p in proofArray], pubs,
+                            transcript_public, device)
 
     @staticmethod
     def prove(zkeyFileName, witnessFileName, logger=None, device: int = 0, blinding: bytes | None = None):
