@@ -339,6 +339,44 @@ int nzcb_wprog_remap(const uint8_t* prog, size_t prog_len, const char* own_sym, 
                      const char* target_sym, size_t target_len, uint8_t** prog_out, size_t* prog_out_len,
                      uint32_t* unmatched, nzcb_err* err);
 
+/* ---- Witness check (snarkjs `wtns check <r1cs> <wtns>`, circom_tester checkConstraints) ----
+ * An iden3 r1cs parsed once and kept resident on `device` (three sparse matrices, the distinct
+ * coefficients in one table), then checked against batches of witnesses: constraint k of
+ * witness w fails iff (A_k . w)(B_k . w) != C_k . w in Fr. An empty side is 0; wire 0 is read
+ * from the witness like any other wire; repeated wires within a side add up; witness values
+ * >= r count modulo r. device = NZCB_R1CS_HOST runs the same functions on the host, so the
+ * library still checks without a GPU; the outputs are the same bytes on both paths and do not
+ * depend on `count`, on the order of the witnesses or on the launch geometry. Unknown
+ * sections of the file are ignored. NZCB_ERR_CURVE when the prime is not BN254's r,
+ * NZCB_ERR_FORMAT for a malformed file (the setup reader's texts) or 2^32 or more terms. */
+#define NZCB_R1CS_HOST (-1)
+typedef struct nzcb_r1cs nzcb_r1cs;
+nzcb_r1cs* nzcb_r1cs_create(const uint8_t* r1cs, size_t len, int device, nzcb_err* err);
+/* The same from a file, memory-mapped (nothing retained after the call). */
+nzcb_r1cs* nzcb_r1cs_create_file(const char* path, int device, nzcb_err* err);
+/* info: n_wires, n_outputs, n_pub_inputs, n_prv_inputs, n_constraints, n_terms,
+ * long_row_threshold (rows with at least that many terms get a wavefront each, the others a
+ * lane), n_long_rows */
+int nzcb_r1cs_info(const nzcb_r1cs* r, uint32_t info[8]);
+typedef struct nzcb_r1cs_result {
+  uint32_t n_bad;     /* failing constraints */
+  uint32_t first_bad; /* the lowest failing index, 0xffffffff when n_bad = 0 */
+} nzcb_r1cs_result;
+/* `count` witnesses against the r1cs. kind: NZCB_WITNESS_WTNS (.wtns bytes, count = 1, n = byte
+ * length), NZCB_WITNESS_HOST or NZCB_WITNESS_DEVICE (n = values per witness; witness i at
+ * witness + i * witness_stride, n x 32-byte LE normal form: what nzcb_wprog_run_dev writes and
+ * nzcb_prove_device reads; device pointers and strides are multiples of 16; witness_stride 0
+ * with count = 1 means 32 n). results: count. bad_out (may be NULL): count x bad_cap u32,
+ * witness i's lowest min(n_bad, bad_cap) failing constraint indices, ascending, the rest
+ * 0xffffffff. Returns 0 whatever the verdicts (count = 0 is fine); NZCB_ERR_WITNESS_LEN
+ * ("Invalid witness length. Circuit: ..., witness: ...") when n is not n_wires. stream: a
+ * hipStream_t to order the work on, NULL = a stream of the call's own; either way the call
+ * owns its buffers, returns with the results on the host and may run while a context proves on
+ * the same device. */
+int nzcb_r1cs_check(nzcb_r1cs* r, const void* witness, size_t n, int kind, int count, size_t witness_stride,
+                    nzcb_r1cs_result* results, uint32_t* bad_out, uint32_t bad_cap, void* stream, nzcb_err* err);
+void nzcb_r1cs_destroy(nzcb_r1cs* r);
+
 /* ---- Setup ------------------------------------------ */
 /* snarkjs `plonk setup <r1cs> <ptau> <zkey>` (snarkjs 0.4.12 plonk_setup.js, run at
  * /root/reference/Makefile:55,60): iden3 r1cs + powers-of-tau file -> snarkjs-0.4 PLONK

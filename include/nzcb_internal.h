@@ -157,6 +157,19 @@ int nzcb_engine_verify_batch(const uint8_t* vk, const uint8_t* proofs, const uin
  * number of values written (cap <= 6). */
 int nzcb_debug_verify_batch_timings(double* ms, int cap);
 
+/* ---- Witness check (csrc/r1cs_check.hip) ---------------------------------------------- */
+/* nzcb_r1cs_create with the tuning knobs: long_row_threshold (0 = the library's constant) and
+ * witness_tile, the most witnesses a lane or wave evaluates per row (0 = the library's, 1; 2 or
+ * 4: tiles of that many, then the smaller tiles for what is left of a batch). The outputs are
+ * the same for every setting. */
+nzcb_r1cs* nzcb_engine_r1cs_create(const uint8_t* r1cs, size_t len, int device, uint32_t long_row_threshold,
+                                   int witness_tile, nzcb_err* err);
+/* Kernel milliseconds (HIP events) of the calling thread's last nzcb_r1cs_check on a device:
+ * [0] the lane-per-row kernel, [1] the wave-per-row kernel, [2] the bitmap collection. Returns
+ * the number of values written (cap <= 3). */
+int nzcb_debug_r1cs_check_timings(double* ms, int cap);
+
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,7 @@
 
 #include "../../include/nzcb_internal.h"
 #include "engine.h"
+#include "r1cs_reader.h"
 
 namespace nzcb {
 void set_err(nzcb_err* err, int code, const char* msg);
@@ -518,59 +519,7 @@ static void synth_setup(int power, int n_public, int n_inputs, uint64_t seed, ui
 // setup's (setup_zkey). Commitments use the coefficient form against tauG1 (section 2),
 // the same group elements snarkjs gets from the Lagrange points (section 12).
 
-struct BinSections {  // iden3 binfile: magic, u32 version, u32 count, (u32 type, u64 size, data)*
-  std::vector<std::pair<const uint8_t*, uint64_t>> sec[16];
-};
-static BinSections read_binfile(const uint8_t* d, size_t len, const char* magic, const char* what) {
-  BinSections b;
-  char msg[96];
-  if (!d || len < 12 || std::memcmp(d, magic, 4) != 0) {
-    std::snprintf(msg, sizeof msg, "%s: invalid file format", what);
-    throw Error(NZCB_ERR_FORMAT, msg);
-  }
-  uint32_t version, nsec;
-  std::memcpy(&version, d + 4, 4);
-  std::memcpy(&nsec, d + 8, 4);
-  size_t off = 12;
-  for (uint32_t i = 0; i < nsec; i++) {
-    if (off + 12 > len) throw Error(NZCB_ERR_FORMAT, "truncated section table");
-    uint32_t type;
-    uint64_t size;
-    std::memcpy(&type, d + off, 4);
-    std::memcpy(&size, d + off + 4, 8);
-    off += 12;
-    if (size > len - off) throw Error(NZCB_ERR_FORMAT, "truncated section");
-    if (type < 16) b.sec[type].push_back({d + off, size});
-    off += size;
-  }
-  return b;
-}
-
-struct ByteReader {
-  const uint8_t* p;
-  uint64_t left;
-  uint32_t u32() {
-    if (left < 4) throw Error(NZCB_ERR_FORMAT, "r1cs: truncated");
-    uint32_t v;
-    std::memcpy(&v, p, 4);
-    p += 4;
-    left -= 4;
-    return v;
-  }
-  uint64_t u64() {
-    const uint64_t lo = u32();
-    return lo | ((uint64_t)u32() << 32);
-  }
-  Fr fr_normal() {  // 32 B LE normal form -> Montgomery (ffjavascript Fr.fromRprLE)
-    if (left < 32) throw Error(NZCB_ERR_FORMAT, "r1cs: truncated");
-    Fr v;
-    std::memcpy(v.v, p, 32);
-    p += 32;
-    left -= 32;
-    if (!(reduce_once(v) == v) || v == Fr::modulus()) throw Error(NZCB_ERR_FORMAT, "r1cs: coefficient not reduced");
-    return to_mont(v);
-  }
-};
+// (the binfile sections, ByteReader and the r1cs header / linear-combination reader: r1cs_reader.h)
 
 struct R1csCircuit {
   Circuit c;
@@ -579,18 +528,8 @@ struct R1csCircuit {
 };
 
 static R1csCircuit circuit_from_r1cs(const uint8_t* d, size_t len) {
-  BinSections b = read_binfile(d, len, "r1cs", "r1cs");
-  if (b.sec[1].empty() || b.sec[2].empty()) throw Error(NZCB_ERR_FORMAT, "r1cs: missing header or constraints");
-  ByteReader h{b.sec[1][0].first, b.sec[1][0].second};
-  if (h.u32() != 32) throw Error(NZCB_ERR_FORMAT, "r1cs: field size is not 32 bytes");
-  if (h.left < 32 || std::memcmp(h.p, FrParams::P, 32) != 0)
-    throw Error(NZCB_ERR_CURVE, "r1cs curve does not match powers of tau ceremony curve");
-  h.p += 32;
-  h.left -= 32;
-  const uint32_t n_wires = h.u32(), n_out = h.u32(), n_pub_in = h.u32();
-  (void)h.u32();  // private inputs
-  (void)h.u64();  // labels
-  const uint32_t n_cons = h.u32();
+  R1csFile f = r1cs_open(d, len, "r1cs curve does not match powers of tau ceremony curve");
+  const uint32_t n_wires = f.n_wires, n_out = f.n_out, n_pub_in = f.n_pub_in, n_cons = f.n_cons;
   R1csCircuit r;
   Circuit& c = r.c;
   r.n_public = n_out + n_pub_in;
@@ -627,18 +566,14 @@ static R1csCircuit circuit_from_r1cs(const uint8_t* d, size_t len) {
     uint32_t s;
     Fr coef, k;
   };
-  ByteReader cr{b.sec[2][0].first, b.sec[2][0].second};
+  ByteReader& cr = f.constraints;
   auto read_lc = [&]() -> Lc {
     Lc lc{0u, Fr::zero(), Fr::zero()};
     std::vector<Term> terms;
-    const uint32_t nt = cr.u32();
-    for (uint32_t i = 0; i < nt; i++) {
-      const uint32_t s = cr.u32();
-      const Fr coef = cr.fr_normal();
-      if (s >= n_wires) throw Error(NZCB_ERR_FORMAT, "r1cs: signal out of range");
+    r1cs_read_lc(cr, n_wires, [&](uint32_t s, const Fr& coef) {
       if (s == 0) lc.k = coef;
       else terms.push_back({s, coef});
-    }
+    });
     const Term t = reduce(terms, 0, terms.size());
     lc.s = t.first;
     lc.coef = t.second;

@@ -692,6 +692,130 @@ napi_value VerifyBatch(napi_env env, napi_callback_info info) {
   return promise;
 }
 
+// one wtns.check call: the r1cs parsed and uploaded (nzcb_r1cs_create_file / nzcb_r1cs_create),
+// the .wtns checked (nzcb_r1cs_check) and the object released, on a worker thread (async
+// work); the promise is settled on the main thread. The inputs are copied.
+struct WtnsCheckWork {
+  napi_deferred deferred = nullptr;
+  napi_async_work work = nullptr;
+  std::string r1cs_path;
+  std::vector<uint8_t> r1cs, wtns;
+  bool from_file = false;
+  int device = 0;
+  uint32_t info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  nzcb_r1cs_result res{0, 0xffffffffu};
+  std::vector<uint32_t> bad;
+  int rc = 0;
+  nzcb_err err{};
+};
+
+void wtns_check_execute(napi_env, void* data) {
+  WtnsCheckWork* w = static_cast<WtnsCheckWork*>(data);
+  nzcb_r1cs* r = w->from_file ? nzcb_r1cs_create_file(w->r1cs_path.c_str(), w->device, &w->err)
+                              : nzcb_r1cs_create(w->r1cs.data(), w->r1cs.size(), w->device, &w->err);
+  if (!r) {
+    w->rc = w->err.code ? w->err.code : NZCB_ERR_INTERNAL;
+    return;
+  }
+  nzcb_r1cs_info(r, w->info);
+  w->rc = nzcb_r1cs_check(r, w->wtns.data(), w->wtns.size(), NZCB_WITNESS_WTNS, 1, 0, &w->res, w->bad.data(),
+                          (uint32_t)w->bad.size(), nullptr, &w->err);
+  nzcb_r1cs_destroy(r);
+}
+
+napi_value u32_array(napi_env env, const uint32_t* v, size_t n) {
+  napi_value arr;
+  napi_create_array_with_length(env, n, &arr);
+  for (size_t i = 0; i < n; i++) {
+    napi_value x;
+    napi_create_uint32(env, v[i], &x);
+    napi_set_element(env, arr, (uint32_t)i, x);
+  }
+  return arr;
+}
+
+void wtns_check_complete(napi_env env, napi_status status, void* data) {
+  WtnsCheckWork* w = static_cast<WtnsCheckWork*>(data);
+  if (status != napi_ok || w->rc != 0) {
+    napi_reject_deferred(env, w->deferred,
+                         make_error(env, w->rc ? w->err.code : NZCB_ERR_INTERNAL,
+                                    w->rc ? w->err.msg : "wtnsCheck: the work was cancelled"));
+  } else {
+    napi_value out, n_bad;
+    napi_create_object(env, &out);
+    napi_create_uint32(env, w->res.n_bad, &n_bad);
+    napi_set_named_property(env, out, "nBad", n_bad);
+    size_t listed = w->res.n_bad < w->bad.size() ? w->res.n_bad : w->bad.size();
+    napi_set_named_property(env, out, "bad", u32_array(env, w->bad.data(), listed));
+    napi_set_named_property(env, out, "info", u32_array(env, w->info, 8));
+    napi_resolve_deferred(env, w->deferred, out);
+  }
+  napi_delete_async_work(env, w->work);
+  delete w;
+}
+
+// wtnsCheck(r1cs: string (file name) | Buffer, wtns: Buffer, device: number, badCap: number)
+//   -> Promise<{nBad, bad: number[] (the lowest badCap failing constraints), info: number[8]}>
+napi_value WtnsCheck(napi_env env, napi_callback_info info) {
+  size_t argc = 4;
+  napi_value argv[4];
+  CHECK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  WtnsCheckWork* w = new WtnsCheckWork();
+  const uint8_t *rb = nullptr, *wb = nullptr;
+  size_t rl = 0, wl = 0;
+  int32_t device = 0, cap = 8;
+  bool ok = argc >= 2 && buf_arg(env, argv[1], &wb, &wl);
+  if (ok && str_arg(env, argv[0], &w->r1cs_path)) {
+    w->from_file = true;
+  } else if (ok && buf_arg(env, argv[0], &rb, &rl)) {
+    w->r1cs.assign(rb, rb + rl);
+  } else {
+    ok = false;
+  }
+  if (argc > 2) napi_get_value_int32(env, argv[2], &device);
+  if (argc > 3) napi_get_value_int32(env, argv[3], &cap);
+  if (!ok || cap < 0) {
+    delete w;
+    napi_throw_type_error(env, nullptr, "wtnsCheck(r1cs: string | Buffer, wtns: Buffer, device?, badCap?)");
+    return nullptr;
+  }
+  w->wtns.assign(wb, wb + wl);
+  w->device = device;
+  w->bad.assign((size_t)cap, 0xffffffffu);
+  napi_value promise, name;
+  if (napi_create_promise(env, &w->deferred, &promise) != napi_ok ||
+      napi_create_string_utf8(env, "nzcb.wtnsCheck", NAPI_AUTO_LENGTH, &name) != napi_ok ||
+      napi_create_async_work(env, nullptr, name, wtns_check_execute, wtns_check_complete, w, &w->work) != napi_ok ||
+      napi_queue_async_work(env, w->work) != napi_ok) {
+    delete w;
+    napi_throw_error(env, nullptr, "nzcb addon: N-API call failed");
+    return nullptr;
+  }
+  return promise;
+}
+
+// r1csInfo(path: string) -> number[8] (nzcb_r1cs_info; parsed on the host, no GPU)
+napi_value R1csInfo(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1];
+  CHECK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  std::string path;
+  if (argc < 1 || !str_arg(env, argv[0], &path)) {
+    napi_throw_type_error(env, nullptr, "r1csInfo(path: string)");
+    return nullptr;
+  }
+  nzcb_err err{};
+  nzcb_r1cs* r = nzcb_r1cs_create_file(path.c_str(), NZCB_R1CS_HOST, &err);
+  if (!r) {
+    napi_throw(env, make_error(env, err.code, err.msg));
+    return nullptr;
+  }
+  uint32_t v[8];
+  nzcb_r1cs_info(r, v);
+  nzcb_r1cs_destroy(r);
+  return u32_array(env, v, 8);
+}
+
 // calldata(proof: Buffer, pub: Buffer) -> string (snarkjs `zkey export soliditycalldata`)
 napi_value Calldata(napi_env env, napi_callback_info info) {
   size_t argc = 2;
@@ -827,6 +951,8 @@ napi_value Init(napi_env env, napi_value exports) {
       {"fullProveDevice", nullptr, FullProveDevice, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"setLanes", nullptr, SetLanes, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"releaseContext", nullptr, ReleaseContext, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"wtnsCheck", nullptr, WtnsCheck, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"r1csInfo", nullptr, R1csInfo, nullptr, nullptr, nullptr, napi_default, nullptr},
   };
   napi_define_properties(env, exports, sizeof(props) / sizeof(props[0]), props);
   return exports;

@@ -11,6 +11,11 @@
 //   node cli.js zkey export verificationkey <circuit.zkey> <verification_key.json>
 //   node cli.js zkey export solidityverifier <circuit.zkey> <Verifier.sol> [contract name]
 //   node cli.js zkey export soliditycalldata <public.json> <proof.json>
+// and `snarkjs wtns check` / `snarkjs r1cs info`:
+//   node cli.js wtns check <circuit.r1cs> <witness.wtns>
+//     (prints "WITNESS IS CORRECT" and exits 0, or "WITNESS CHECKING FAILED" with the failing
+//     constraints and exit code 1; NZCB_DEVICE=-1 checks on the host)
+//   node cli.js r1cs info  <circuit.r1cs>
 // Output JSON is written like snarkjs's CLI (stringifyBigInts, 1-space indent).
 const fs = require('fs');
 const nz = require('./index.js');
@@ -22,7 +27,9 @@ function usage() {
                 '       cli.js plonk verify <verification_key.json> <public.json> <proof.json>\n' +
                 '       cli.js zkey export verificationkey <zkey> <verification_key.json>\n' +
                 '       cli.js zkey export solidityverifier <zkey> <verifier.sol> [contract name]\n' +
-                '       cli.js zkey export soliditycalldata <public.json> <proof.json>');
+                '       cli.js zkey export soliditycalldata <public.json> <proof.json>\n' +
+                '       cli.js wtns check <r1cs> <wtns>\n' +
+                '       cli.js r1cs info <r1cs>');
   process.exit(1);
 }
 
@@ -45,6 +52,16 @@ async function zkeyExport(argv) {
 
 async function main(argv) {
   if (argv[0] === 'zkey') return zkeyExport(argv);
+  if (argv[0] === 'wtns' && argv[1] === 'check' && argv.length === 4) {
+    const say = { info: (m) => console.log(m), warn: (m) => console.log(m), debug: () => {} };
+    const device = process.env.NZCB_DEVICE === undefined ? 0 : Number(process.env.NZCB_DEVICE);
+    const ok = await nz.wtns.check(argv[2], argv[3], say, { device });
+    process.exit(ok ? 0 : 1);
+  }
+  if (argv[0] === 'r1cs' && argv[1] === 'info' && argv.length === 3) {
+    await nz.r1cs.info(argv[2], { info: (m) => console.log(m) });
+    return;
+  }
   if (argv[0] !== 'plonk') usage();
   const logger = process.env.NZCB_VERBOSE ? { debug: (m) => console.error(m) } : null;
   let res, out;

@@ -468,6 +468,50 @@ async function verifyBatch(vkVerifier, publicSignalsArray, proofArray, logger, o
   return ok;
 }
 
+// snarkjs wtns.check(r1csFileName, wtnsFileName, logger) (`snarkjs wtns check`): does the
+// witness satisfy every constraint of the r1cs? On the GPU (include/nzcb.h nzcb_r1cs_check), on
+// a worker thread. Resolves to true / false and logs snarkjs's lines: "WITNESS IS CORRECT", or
+// "WITNESS CHECKING FAILED" and one line per listed failing constraint. options: {device
+// (default 0; -1 = on the host), badCap (how many failing constraints to list, default 8)}.
+function warnFn(logger) {
+  if (logger && typeof logger.warn === 'function') return (m) => logger.warn(m);
+  return loggerFn(logger);
+}
+async function wtnsCheck(r1csFileName, wtnsFileName, logger, options) {
+  options = options || {};
+  const log = loggerFn(logger);
+  const info = logger && typeof logger.info === 'function' ? (m) => logger.info(m) : log;
+  const warn = warnFn(logger);
+  const r1cs = typeof r1csFileName === 'string' ? r1csFileName : readBin(r1csFileName);
+  const res = await addon.wtnsCheck(r1cs, readBin(wtnsFileName), options.device === undefined ? 0 : options.device,
+    options.badCap === undefined ? 8 : options.badCap);
+  if (res.nBad === 0) {
+    if (info) info('WITNESS IS CORRECT');
+    return true;
+  }
+  if (warn) {
+    warn('WITNESS CHECKING FAILED');
+    for (const k of res.bad) warn(`constraint ${k} is not satisfied`);
+    if (res.nBad > res.bad.length) warn(`${res.nBad} constraints are not satisfied`);
+  }
+  return false;
+}
+
+// snarkjs r1cs.info(r1csFileName): the circuit's sizes (host only, no GPU)
+async function r1csInfo(r1csFileName, logger) {
+  const v = addon.r1csInfo(r1csFileName);
+  const out = { nVars: v[0], nOutputs: v[1], nPubInputs: v[2], nPrvInputs: v[3], nConstraints: v[4] };
+  const log = logger && typeof logger.info === 'function' ? (m) => logger.info(m) : loggerFn(logger);
+  if (log) {
+    log(`# of Wires: ${out.nVars}`);
+    log(`# of Constraints: ${out.nConstraints}`);
+    log(`# of Private Inputs: ${out.nPrvInputs}`);
+    log(`# of Public Inputs: ${out.nPubInputs}`);
+    log(`# of Outputs: ${out.nOutputs}`);
+  }
+  return out;
+}
+
 async function exportSolidityCallData(proof, publicSignals) {
   return addon.calldata(proofBuf(proof), pubBuf(publicSignals));
 }
@@ -527,7 +571,8 @@ module.exports = {
   plonk: { setup, prove, fullProve, verify, verifyBatch, exportSolidityCallData },
   zKey: { exportVerificationKey, exportSolidityVerifier },
   nzcp: Object.assign({}, require('./nzcp.js'), { witness: nzcpWitness }),
-  wtns: { calculate: wtnsCalculate, remapProgram },
+  wtns: { calculate: wtnsCalculate, remapProgram, check: wtnsCheck },
+  r1cs: { info: r1csInfo },
   version: addon.version,
   deviceCount: addon.deviceCount,
   _addon: addon,

@@ -47,12 +47,16 @@ EXPORTED_SYMBOLS = [
     "nzcb_debug_guard_check", "nzcb_debug_guard_selftest", "nzcb_debug_inject_fault", "nzcb_debug_f29",
     "nzcb_msm_table_create_lagrange",
     "nzcb_verify_batch", "nzcb_engine_g1_lincomb", "nzcb_engine_verify_batch", "nzcb_debug_verify_batch_timings",
+    "nzcb_r1cs_create", "nzcb_r1cs_create_file", "nzcb_r1cs_info", "nzcb_r1cs_check", "nzcb_r1cs_destroy",
+    "nzcb_engine_r1cs_create", "nzcb_debug_r1cs_check_timings",
 ]
 
 NZCB_FAULT_QUOTIENT = 1  # include/nzcb_internal.h
 NZCB_DEBUG_GENERIC_K = 2  # include/nzcb_internal.h
 NZCB_FAULT_LANE_ALLOC = 3  # include/nzcb_internal.h
 VERIFY_HOST = -1  # include/nzcb.h NZCB_VERIFY_HOST: verify_batch with the scalar multiplications on the host
+R1CS_HOST = -1  # include/nzcb.h NZCB_R1CS_HOST: the witness check on the host
+WITNESS_WTNS, WITNESS_HOST, WITNESS_DEVICE = 0, 1, 2  # include/nzcb.h NZCB_WITNESS_*
 
 
 def lagrange_commit_enabled() -> bool:
@@ -247,6 +251,14 @@ def load(path: str | None = None):
         "nzcb_engine_verify_batch": (c_int, [u8p, u8p, u8p, c_size_t, c_int, c_int, c_int, c_int, u8p, POINTER(c_int),
                                              u8p, POINTER(c_int), POINTER(_Err)]),
         "nzcb_debug_verify_batch_timings": (c_int, [POINTER(c_double), c_int]),
+        "nzcb_r1cs_create": (c_void_p, [ctypes.c_char_p, c_size_t, c_int, POINTER(_Err)]),
+        "nzcb_r1cs_create_file": (c_void_p, [ctypes.c_char_p, c_int, POINTER(_Err)]),
+        "nzcb_engine_r1cs_create": (c_void_p, [ctypes.c_char_p, c_size_t, c_int, c_uint32, c_int, POINTER(_Err)]),
+        "nzcb_r1cs_info": (c_int, [c_void_p, POINTER(c_uint32)]),
+        "nzcb_r1cs_check": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_size_t, POINTER(c_uint32),
+                                    POINTER(c_uint32), c_uint32, c_void_p, POINTER(_Err)]),
+        "nzcb_r1cs_destroy": (None, [c_void_p]),
+        "nzcb_debug_r1cs_check_timings": (c_int, [POINTER(c_double), c_int]),
     }
     lib.missing_symbols = []
     for name, (res, args) in sigs.items():
@@ -834,6 +846,96 @@ class WitnessProgram:
         _check(self.lib.nzcb_wprog_run_dev(self.h, dev_inputs, count, dev_witness, stride, st, None,
                                            ctypes.byref(err)), err)
         return [st[i] for i in range(count)]
+
+
+class R1cs:
+    """An r1cs resident on the GPU and the witness check against it (include/nzcb.h
+    nzcb_r1cs_*; snarkjs ``wtns check``). data_or_path: the iden3 r1cs bytes, or a file name
+    (memory-mapped). device = R1CS_HOST (-1) runs the same check on the host. ``info`` holds
+    n_wires, n_outputs, n_pub_inputs, n_prv_inputs, n_constraints, n_terms, long_row_threshold
+    and n_long_rows. long_row_threshold / witness_tile: tuning knobs (include/nzcb_internal.h
+    nzcb_engine_r1cs_create); the results do not depend on them."""
+
+    INFO = ("n_wires", "n_outputs", "n_pub_inputs", "n_prv_inputs", "n_constraints", "n_terms",
+            "long_row_threshold", "n_long_rows")
+
+    def __init__(self, data_or_path, device: int = 0, long_row_threshold: int = 0, witness_tile: int = 0):
+        self.lib = load()
+        self.device = device
+        err = _Err()
+        if isinstance(data_or_path, (bytes, bytearray, memoryview)):
+            data = bytes(data_or_path)
+            if long_row_threshold or witness_tile:
+                self.h = self.lib.nzcb_engine_r1cs_create(data, len(data), device, long_row_threshold, witness_tile,
+                                                          ctypes.byref(err))
+            else:
+                self.h = self.lib.nzcb_r1cs_create(data, len(data), device, ctypes.byref(err))
+        elif long_row_threshold or witness_tile:
+            raise ValueError("the tuning knobs take the r1cs as bytes")
+        else:
+            self.h = self.lib.nzcb_r1cs_create_file(os.fsencode(data_or_path), device, ctypes.byref(err))
+        if not self.h:
+            raise NzcbError(err.code, err.msg.decode(errors="replace"))
+        info = (c_uint32 * 8)()
+        self.lib.nzcb_r1cs_info(self.h, info)
+        self.info = dict(zip(self.INFO, list(info)))
+        self.n_wires = self.info["n_wires"]
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.nzcb_r1cs_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def _check(self, witness, n: int, kind: int, count: int, stride: int, bad_cap: int) -> list:
+        res = (c_uint32 * (2 * max(count, 1)))()
+        bad = (c_uint32 * max(count * bad_cap, 1))()
+        err = _Err()
+        _check(self.lib.nzcb_r1cs_check(self.h, witness, n, kind, count, stride, res, bad, bad_cap, None,
+                                        ctypes.byref(err)), err)
+        out = []
+        for i in range(count):
+            n_bad = res[2 * i]
+            out.append({"n_bad": n_bad, "first_bad": res[2 * i + 1] if n_bad else None,
+                        "bad": list(bad[i * bad_cap:i * bad_cap + min(n_bad, bad_cap)])})
+        return out
+
+    def check(self, witnesses, count=None, bad_cap: int = 8, stride=None) -> list:
+        """witnesses: .wtns bytes (one witness), or `count` witnesses of 32-byte LE values,
+        witness i at byte i * stride (default: packed, and count = all that the bytes hold).
+        Returns one dict per witness: n_bad, first_bad (None when satisfied) and bad, the lowest
+        min(n_bad, bad_cap) failing constraint indices in ascending order."""
+        data = bytes(witnesses)
+        if data[:4] == b"wtns":
+            return self._check(data, len(data), WITNESS_WTNS, 1, 0, bad_cap)
+        wbytes = 32 * self.n_wires
+        if stride is not None:
+            n = self.n_wires
+            if count is None:
+                count = (len(data) + stride - wbytes) // stride if stride else 0
+            if count and (count - 1) * stride + wbytes > len(data):
+                raise ValueError("the witnesses do not fit the buffer")
+        else:
+            if count is None:
+                count = len(data) // wbytes if wbytes and len(data) % wbytes == 0 else 1
+            n = len(data) // 32 // count if count else self.n_wires
+            stride = 32 * n
+            if count and len(data) != count * stride:
+                raise ValueError("the buffer is not `count` witnesses of whole values")
+        return self._check(data, n, WITNESS_HOST, count, stride, bad_cap)
+
+    def check_dev(self, dev_witness: int, count: int, stride: int, bad_cap: int = 8) -> list:
+        """`count` witnesses in HBM, witness i at dev_witness + i * stride (what
+        WitnessProgram.run_dev writes), checked in place."""
+        return self._check(c_void_p(dev_witness), self.n_wires, WITNESS_DEVICE, count, stride, bad_cap)
+
+    @staticmethod
+    def timings() -> list:
+        """Kernel ms of this thread's last device check: lane-per-row, wave-per-row, collect."""
+        ms = (c_double * 3)()
+        n = load().nzcb_debug_r1cs_check_timings(ms, 3)
+        return list(ms)[:n]
 
 
 def wprog_remap(program: bytes, own_sym: bytes, target_sym: bytes) -> bytes:
