@@ -377,6 +377,37 @@ int nzcb_r1cs_check(nzcb_r1cs* r, const void* witness, size_t n, int kind, int c
                     nzcb_r1cs_result* results, uint32_t* bad_out, uint32_t bad_cap, void* stream, nzcb_err* err);
 void nzcb_r1cs_destroy(nzcb_r1cs* r);
 
+/* ---- Pass signature (COSE ES256) ------------------------------------------------------ */
+/* ECDSA over NIST P-256 with SHA-256, the signature of an NZ COVID Pass, verified in batches
+ * (csrc/p256_verify.hip). The circuit does not check it; @vaxxnz/nzcp's verifyPassURIOffline
+ * did that in the reference's flow. A key object validates a public key (coordinates below p,
+ * on the curve, not (0, 0); otherwise NZCB_ERR_ARG "public key is not a point on P-256") and
+ * keeps fixed-base window tables for G and for the key (about 1 MB) resident on GPU `device`,
+ * built there; device = NZCB_P256_HOST builds them on the host with the same functions and
+ * verifies there. Whether the key is to be trusted (the issuer's DID document) is the caller's
+ * business. All byte strings are big-endian, as in a JWK, a COSE signature and a SHA-256
+ * digest: pub_xy = x || y. */
+#define NZCB_P256_HOST (-1)
+enum { NZCB_SIG_OK = 0, NZCB_SIG_INVALID = 1, NZCB_SIG_RANGE = 2 }; /* RANGE: r or s not in [1, n-1] */
+typedef struct nzcb_p256_key nzcb_p256_key;
+nzcb_p256_key* nzcb_p256_key_create(const uint8_t pub_xy[64], int device, nzcb_err* err);
+/* status_out[i] (host memory) = NZCB_SIG_* for hash i, 32 bytes at hashes + i * hash_stride
+ * (the SHA-256 of the pass's COSE Sig_structure; a hash >= n counts modulo n), and signature i,
+ * r || s at sigs + i * sig_stride. Standard ECDSA: no low-s rule. on_device: both are HBM
+ * pointers on the key's device, pointers and strides multiples of 4, read in place: hashes =
+ * dev_records + offsetof(nzcb_nzcp_record, tbs_sha256) with hash_stride =
+ * sizeof(nzcb_nzcp_record) verifies what nzcb_nzcp_witness_dev wrote (a host key object
+ * cannot); such buffers must be complete when the call starts, or their producer enqueued on
+ * the same `stream` before it (a stream of the call's own waits for no other stream, and
+ * nzcb_nzcp_witness_dev is asynchronous). Host buffers may have any strides >= 32 and 64. Returns 0 whatever the verdicts
+ * (count = 0 is fine) and the statuses do not depend on the batch, its order or the path; the
+ * call owns its device buffers, runs on `stream` (a HIP stream of the key's device) or on a
+ * stream of its own, returns with the statuses on the host, and may run while a context
+ * proves on the same device. */
+int nzcb_p256_verify(nzcb_p256_key* k, const void* hashes, size_t hash_stride, const void* sigs, size_t sig_stride,
+                     int count, int on_device, int32_t* status_out, void* stream, nzcb_err* err);
+void nzcb_p256_key_destroy(nzcb_p256_key* k);
+
 /* ---- Setup ------------------------------------------ */
 /* snarkjs `plonk setup <r1cs> <ptau> <zkey>` (snarkjs 0.4.12 plonk_setup.js, run at
  * /root/reference/Makefile:55,60): iden3 r1cs + powers-of-tau file -> snarkjs-0.4 PLONK

@@ -169,6 +169,32 @@ nzcb_r1cs* nzcb_engine_r1cs_create(const uint8_t* r1cs, size_t len, int device, 
  * the number of values written (cap <= 3). */
 int nzcb_debug_r1cs_check_timings(double* ms, int cap);
 
+/* ---- Pass signature (csrc/p256.h, csrc/p256_verify.hip) -------------------------------- */
+/* nzcb_p256_key_create with the window width of the fixed-base tables: 4 or 8 (0 = the
+ * library's default). The statuses do not depend on it. */
+nzcb_p256_key* nzcb_engine_p256_key_create(const uint8_t pub_xy[64], int device, int window, nzcb_err* err);
+/* The P-256 field arithmetic as compiled for `device` (or for the host, NZCB_P256_HOST):
+ * out[i] = a[i] op b[i] in F_p (field 0) or F_n (field 1), `count` <= 2^24 operands of 32
+ * big-endian bytes each in normal form, below the modulus (NZCB_ERR_ARG otherwise); sqr and
+ * inv read a only (inv: 0 -> 0). Products go through the Montgomery form and back. */
+#define NZCB_P256_OP_ADD 0
+#define NZCB_P256_OP_SUB 1
+#define NZCB_P256_OP_MUL 2
+#define NZCB_P256_OP_SQR 3
+#define NZCB_P256_OP_INV 4
+int nzcb_debug_p256_field(int device, int op, int field, const uint8_t* a, const uint8_t* b, size_t count,
+                          uint8_t* out, nzcb_err* err);
+/* out_xy[i] = u1[i] G + u2[i] Q, affine x || y (64 zero bytes for the point at infinity), for
+ * the key object's Q, device and window, through the table code the verifier runs. u1, u2:
+ * `count` <= 2^24 scalars of 32 big-endian bytes (any 256-bit value). */
+int nzcb_debug_p256_mul2(nzcb_p256_key* k, const uint8_t* u1, const uint8_t* u2, size_t count, uint8_t* out_xy,
+                         nzcb_err* err);
+/* Milliseconds of the calling thread's last calls: [0] the table build of nzcb_p256_key_create
+ * (the kernel, HIP events; wall time on the host path), [1] the verify kernel of
+ * nzcb_p256_verify (HIP events; 0 on the host path), [2] that call's wall time. Returns the
+ * number of values written (cap <= 3). */
+int nzcb_debug_p256_timings(double* ms, int cap);
+
 
 #ifdef __cplusplus
 }

@@ -794,6 +794,85 @@ napi_value WtnsCheck(napi_env env, napi_callback_info info) {
   return promise;
 }
 
+// one p256Verify call: the key's tables built (nzcb_p256_key_create), the batch verified
+// (nzcb_p256_verify) and the key released, on a worker thread (async work); the promise is
+// settled on the main thread. The inputs are copied.
+struct P256VerifyWork {
+  napi_deferred deferred = nullptr;
+  napi_async_work work = nullptr;
+  uint8_t key[64];
+  std::vector<uint8_t> hashes, sigs;
+  std::vector<int32_t> status;
+  int device = 0;
+  int rc = 0;
+  nzcb_err err{};
+};
+
+void p256_verify_execute(napi_env, void* data) {
+  P256VerifyWork* w = static_cast<P256VerifyWork*>(data);
+  nzcb_p256_key* k = nzcb_p256_key_create(w->key, w->device, &w->err);
+  if (!k) {
+    w->rc = w->err.code ? w->err.code : NZCB_ERR_INTERNAL;
+    return;
+  }
+  w->rc = nzcb_p256_verify(k, w->hashes.data(), 32, w->sigs.data(), 64, (int)w->status.size(), 0, w->status.data(),
+                           nullptr, &w->err);
+  nzcb_p256_key_destroy(k);
+}
+
+void p256_verify_complete(napi_env env, napi_status status, void* data) {
+  P256VerifyWork* w = static_cast<P256VerifyWork*>(data);
+  if (status != napi_ok || w->rc != 0) {
+    napi_reject_deferred(env, w->deferred,
+                         make_error(env, w->rc ? w->err.code : NZCB_ERR_INTERNAL,
+                                    w->rc ? w->err.msg : "p256Verify: the work was cancelled"));
+  } else {
+    napi_value arr;
+    napi_create_array_with_length(env, w->status.size(), &arr);
+    for (size_t i = 0; i < w->status.size(); i++) {
+      napi_value x;
+      napi_create_int32(env, w->status[i], &x);
+      napi_set_element(env, arr, (uint32_t)i, x);
+    }
+    napi_resolve_deferred(env, w->deferred, arr);
+  }
+  napi_delete_async_work(env, w->work);
+  delete w;
+}
+
+// p256Verify(key: Buffer (x || y, 64 bytes), hashes: Buffer (32 n), sigs: Buffer (64 n), device: number)
+//   -> Promise<number[n]> (NZCB_SIG_*); device -1 is the host path
+napi_value P256Verify(napi_env env, napi_callback_info info) {
+  size_t argc = 4;
+  napi_value argv[4];
+  CHECK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  const uint8_t *kb = nullptr, *hb = nullptr, *sb = nullptr;
+  size_t kl = 0, hl = 0, sl = 0;
+  int32_t device = 0;
+  if (argc > 3) napi_get_value_int32(env, argv[3], &device);
+  if (argc < 3 || !buf_arg(env, argv[0], &kb, &kl) || !buf_arg(env, argv[1], &hb, &hl) ||
+      !buf_arg(env, argv[2], &sb, &sl) || kl != 64 || hl % 32 || sl != hl * 2) {
+    napi_throw_type_error(env, nullptr, "p256Verify(key: Buffer(64), hashes: Buffer(32 n), sigs: Buffer(64 n), device?)");
+    return nullptr;
+  }
+  P256VerifyWork* w = new P256VerifyWork();
+  memcpy(w->key, kb, 64);
+  w->hashes.assign(hb, hb + hl);
+  w->sigs.assign(sb, sb + sl);
+  w->status.assign(hl / 32, NZCB_SIG_INVALID);
+  w->device = device;
+  napi_value promise, name;
+  if (napi_create_promise(env, &w->deferred, &promise) != napi_ok ||
+      napi_create_string_utf8(env, "nzcb.p256Verify", NAPI_AUTO_LENGTH, &name) != napi_ok ||
+      napi_create_async_work(env, nullptr, name, p256_verify_execute, p256_verify_complete, w, &w->work) != napi_ok ||
+      napi_queue_async_work(env, w->work) != napi_ok) {
+    delete w;
+    napi_throw_error(env, nullptr, "nzcb addon: N-API call failed");
+    return nullptr;
+  }
+  return promise;
+}
+
 // r1csInfo(path: string) -> number[8] (nzcb_r1cs_info; parsed on the host, no GPU)
 napi_value R1csInfo(napi_env env, napi_callback_info info) {
   size_t argc = 1;
@@ -953,6 +1032,7 @@ napi_value Init(napi_env env, napi_value exports) {
       {"releaseContext", nullptr, ReleaseContext, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"wtnsCheck", nullptr, WtnsCheck, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"r1csInfo", nullptr, R1csInfo, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"p256Verify", nullptr, P256Verify, nullptr, nullptr, nullptr, napi_default, nullptr},
   };
   napi_define_properties(env, exports, sizeof(props) / sizeof(props[0]), props);
   return exports;

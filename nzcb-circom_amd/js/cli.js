@@ -16,6 +16,11 @@
 //     (prints "WITNESS IS CORRECT" and exits 0, or "WITNESS CHECKING FAILED" with the failing
 //     constraints and exit code 1; NZCB_DEVICE=-1 checks on the host)
 //   node cli.js r1cs info  <circuit.r1cs>
+// and the signature check of NZ COVID Passes (what verifyPassURIOffline does in the reference's tests):
+//   node cli.js nzcp verify <file with one pass URI per line> [example | <x> <y>]
+//     (the issuer's P-256 key as base64url JWK coordinates, default the specification's example
+//     key; prints "OK", "INVALID SIGNATURE" or the reason per pass and exits 0 only if all are
+//     valid; NZCB_DEVICE=-1 verifies on the host)
 // Output JSON is written like snarkjs's CLI (stringifyBigInts, 1-space indent).
 const fs = require('fs');
 const nz = require('./index.js');
@@ -29,7 +34,8 @@ function usage() {
                 '       cli.js zkey export solidityverifier <zkey> <verifier.sol> [contract name]\n' +
                 '       cli.js zkey export soliditycalldata <public.json> <proof.json>\n' +
                 '       cli.js wtns check <r1cs> <wtns>\n' +
-                '       cli.js r1cs info <r1cs>');
+                '       cli.js r1cs info <r1cs>\n' +
+                '       cli.js nzcp verify <file with one pass URI per line> [example | <x> <y>]');
   process.exit(1);
 }
 
@@ -61,6 +67,15 @@ async function main(argv) {
   if (argv[0] === 'r1cs' && argv[1] === 'info' && argv.length === 3) {
     await nz.r1cs.info(argv[2], { info: (m) => console.log(m) });
     return;
+  }
+  if (argv[0] === 'nzcp' && argv[1] === 'verify' && (argv.length === 3 || argv.length === 4 || argv.length === 5)) {
+    if (argv.length === 4 && argv[3] !== 'example') usage();
+    const key = argv.length === 5 ? { x: argv[3], y: argv[4] } : 'example';
+    const device = process.env.NZCB_DEVICE === undefined ? 0 : Number(process.env.NZCB_DEVICE);
+    const uris = fs.readFileSync(argv[2], 'utf8').split(/\r?\n/).map((l) => l.trim()).filter((l) => l);
+    const res = await nz.nzcp.verifyPasses(uris, { key, device });
+    for (const r of res) console.log(r.valid ? 'OK' : (r.status === 1 ? 'INVALID SIGNATURE' : r.reason));
+    process.exit(res.length && res.every((r) => r.valid) ? 0 : 1);
   }
   if (argv[0] !== 'plonk') usage();
   const logger = process.env.NZCB_VERBOSE ? { debug: (m) => console.error(m) } : null;

@@ -567,10 +567,98 @@ function nzcpWitness(inputs, options) {
   return Array.isArray(inputs) ? out : out[0];
 }
 
+// Pass signatures (include/nzcb.h nzcb_p256_*): COSE ES256 = ECDSA P-256 over the SHA-256 of the
+// Sig_structure, what @vaxxnz/nzcp's verifyPassURIOffline checks in the reference's tests
+// (test/nzcp.js:16) before a pass is used. options.key: {x, y} base64url as in a DID
+// document's publicKeyJwk, a 64-byte Buffer x || y, or 'example' (nzcp.EXAMPLE_PUBLIC_KEY);
+// whether a key is the issuer's is the caller's business. options.device: the GPU (default 0),
+// -1 = the host path. options.now (seconds): adds expired / notYetValid. Resolves to one object
+// per pass: {valid, status (0 ok, 1 invalid, 2 r or s out of range, null = not verified), reason,
+// alg, kid, iss, nbf, exp}; a pass that is malformed, not ES256 or whose signature is not 64
+// bytes is reported with its reason and not sent to the verifier.
+const nzcpHost = require('./nzcp.js');
+const SIG_REASON = [null, 'invalid signature', 'signature out of range'];
+
+function b64url(s) {
+  return Buffer.from(String(s).replace(/-/g, '+').replace(/_/g, '/'), 'base64');
+}
+
+function p256KeyBuffer(key) {
+  if (key === 'example') key = nzcpHost.EXAMPLE_PUBLIC_KEY;
+  if (Buffer.isBuffer(key) || key instanceof Uint8Array) {
+    if (key.length !== 64) throw new Error('a P-256 public key is 32 + 32 bytes');
+    return Buffer.from(key);
+  }
+  if (!key || key.x === undefined || key.y === undefined) {
+    throw new Error("verifyPass needs options.key: {x, y}, a 64-byte Buffer or 'example'");
+  }
+  const x = b64url(key.x);
+  const y = b64url(key.y);
+  if (x.length !== 32 || y.length !== 32) throw new Error('a P-256 public key is 32 + 32 bytes');
+  return Buffer.concat([x, y]);
+}
+
+// SHA-256 digests (32 bytes each) against r || s signatures (64 bytes each) -> status numbers
+async function p256Verify(key, hashes, sigs, options) {
+  options = options || {};
+  return addon.p256Verify(p256KeyBuffer(key), Buffer.concat(hashes), Buffer.concat(sigs),
+    options.device === undefined ? 0 : options.device);
+}
+
+async function verifyPasses(uris, options) {
+  options = options || {};
+  const key = p256KeyBuffer(options.key);
+  const out = [];
+  const sent = [];
+  const hashes = [];
+  const sigs = [];
+  for (const uri of uris) {
+    const d = { valid: false, status: null, reason: null, alg: null, kid: null, iss: null, nbf: null, exp: null };
+    out.push(d);
+    let pass;
+    try {
+      pass = nzcpHost.decodePass(uri);
+      Object.assign(d, nzcpHost.protectedHeader(uri));
+      const [cwt] = nzcpHost.cborDecode(pass.payload, 0);
+      Object.assign(d, { iss: cwt.get(1), nbf: cwt.get(5), exp: cwt.get(4) });
+    } catch (e) {
+      d.reason = `malformed pass: ${e.message}`;
+      continue;
+    }
+    if (options.now !== undefined) {
+      d.expired = typeof d.exp === 'number' && options.now >= d.exp;
+      d.notYetValid = typeof d.nbf === 'number' && options.now < d.nbf;
+    }
+    if (d.alg !== -7) {
+      d.reason = `unsupported alg ${d.alg} (ES256 is -7)`;
+    } else if (!Buffer.isBuffer(pass.signature) || pass.signature.length !== 64) {
+      d.reason = 'signature is not 64 bytes';
+    } else {
+      hashes.push(crypto.createHash('sha256').update(nzcpHost.toBeSigned(uri)).digest());
+      sigs.push(pass.signature);
+      sent.push(d);
+    }
+  }
+  if (sent.length) {
+    const st = await addon.p256Verify(key, Buffer.concat(hashes), Buffer.concat(sigs),
+      options.device === undefined ? 0 : options.device);
+    sent.forEach((d, i) => {
+      d.status = st[i];
+      d.valid = st[i] === 0;
+      d.reason = SIG_REASON[st[i]];
+    });
+  }
+  return out;
+}
+
+async function verifyPass(uri, options) {
+  return (await verifyPasses([uri], options))[0];
+}
+
 module.exports = {
   plonk: { setup, prove, fullProve, verify, verifyBatch, exportSolidityCallData },
   zKey: { exportVerificationKey, exportSolidityVerifier },
-  nzcp: Object.assign({}, require('./nzcp.js'), { witness: nzcpWitness }),
+  nzcp: Object.assign({}, nzcpHost, { witness: nzcpWitness, verifyPass, verifyPasses, p256Verify }),
   wtns: { calculate: wtnsCalculate, remapProgram, check: wtnsCheck },
   r1cs: { info: r1csInfo },
   version: addon.version,

@@ -103,6 +103,19 @@ function toBeSigned(passURI) {
     cborBytes(Buffer.alloc(0)), cborBytes(payload)]);
 }
 
+// the COSE protected header of a pass: {alg (-7 = ES256), kid}
+function protectedHeader(passURI) {
+  const [hdr] = cborDecode(decodePass(passURI).bodyProtected, 0);
+  if (!(hdr instanceof Map)) throw new Error('the protected header is not a map');
+  const kid = hdr.get(4);
+  return { alg: hdr.get(1), kid: Buffer.isBuffer(kid) ? kid.toString('utf8') : kid };
+}
+
+// The NZCP specification's example issuer key "key-1" (JWK coordinates, base64url), under
+// which the specification's example passes verify. The live key is not here: callers supply
+// the keys they trust.
+const EXAMPLE_PUBLIC_KEY = { x: 'zRR-XGsCp12Vvbgui4DD6O6cqmhfPuXMhi1OxPl8760', y: 'Iv5SU6FuW-TRYh5_GOrJlcV_gpF_GpFQhCOD8LSk3T0' };
+
 function claims(passURI) {
   const { payload } = decodePass(passURI);
   const [cwt] = cborDecode(payload, 0);
@@ -171,5 +184,6 @@ function expectedPublicSignals(passURI, data) {
 
 module.exports = {
   base32Decode, cborDecode, decodePass, toBeSigned, claims, circuitInput, expectedPublicSignals,
+  protectedHeader, EXAMPLE_PUBLIC_KEY,
   evmRearrange, LIVE_TOBESIGNED_MAX, EXAMPLE_TOBESIGNED_MAX,
 };

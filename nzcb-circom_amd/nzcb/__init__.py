@@ -49,6 +49,8 @@ EXPORTED_SYMBOLS = [
     "nzcb_verify_batch", "nzcb_engine_g1_lincomb", "nzcb_engine_verify_batch", "nzcb_debug_verify_batch_timings",
     "nzcb_r1cs_create", "nzcb_r1cs_create_file", "nzcb_r1cs_info", "nzcb_r1cs_check", "nzcb_r1cs_destroy",
     "nzcb_engine_r1cs_create", "nzcb_debug_r1cs_check_timings",
+    "nzcb_p256_key_create", "nzcb_p256_verify", "nzcb_p256_key_destroy", "nzcb_engine_p256_key_create",
+    "nzcb_debug_p256_field", "nzcb_debug_p256_mul2", "nzcb_debug_p256_timings",
 ]
 
 NZCB_FAULT_QUOTIENT = 1  # include/nzcb_internal.h
@@ -57,6 +59,9 @@ NZCB_FAULT_LANE_ALLOC = 3  # include/nzcb_internal.h
 VERIFY_HOST = -1  # include/nzcb.h NZCB_VERIFY_HOST: verify_batch with the scalar multiplications on the host
 R1CS_HOST = -1  # include/nzcb.h NZCB_R1CS_HOST: the witness check on the host
 WITNESS_WTNS, WITNESS_HOST, WITNESS_DEVICE = 0, 1, 2  # include/nzcb.h NZCB_WITNESS_*
+P256_HOST = -1  # include/nzcb.h NZCB_P256_HOST: signature verification on the host
+SIG_OK, SIG_INVALID, SIG_RANGE = 0, 1, 2  # include/nzcb.h NZCB_SIG_*
+P256_OPS = {"add": 0, "sub": 1, "mul": 2, "sqr": 3, "inv": 4}  # include/nzcb_internal.h NZCB_P256_OP_*
 
 
 def lagrange_commit_enabled() -> bool:
@@ -259,6 +264,15 @@ def load(path: str | None = None):
                                     POINTER(c_uint32), c_uint32, c_void_p, POINTER(_Err)]),
         "nzcb_r1cs_destroy": (None, [c_void_p]),
         "nzcb_debug_r1cs_check_timings": (c_int, [POINTER(c_double), c_int]),
+        "nzcb_p256_key_create": (c_void_p, [ctypes.c_char_p, c_int, POINTER(_Err)]),
+        "nzcb_engine_p256_key_create": (c_void_p, [ctypes.c_char_p, c_int, c_int, POINTER(_Err)]),
+        "nzcb_p256_verify": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_int, c_int,
+                                     POINTER(ctypes.c_int32), c_void_p, POINTER(_Err)]),
+        "nzcb_p256_key_destroy": (None, [c_void_p]),
+        "nzcb_debug_p256_field": (c_int, [c_int, c_int, c_int, ctypes.c_char_p, ctypes.c_char_p, c_size_t, u8p,
+                                          POINTER(_Err)]),
+        "nzcb_debug_p256_mul2": (c_int, [c_void_p, ctypes.c_char_p, ctypes.c_char_p, c_size_t, u8p, POINTER(_Err)]),
+        "nzcb_debug_p256_timings": (c_int, [POINTER(c_double), c_int]),
     }
     lib.missing_symbols = []
     for name, (res, args) in sigs.items():
@@ -935,6 +949,171 @@ class R1cs:
         """Kernel ms of this thread's last device check: lane-per-row, wave-per-row, collect."""
         ms = (c_double * 3)()
         n = load().nzcb_debug_r1cs_check_timings(ms, 3)
+        return list(ms)[:n]
+
+
+def _b64url(s: str) -> bytes:
+    import base64
+    return base64.urlsafe_b64decode(s + "=" * (-len(s) % 4))
+
+
+def p256_field(op: str, field: str, a, b=None, device: int = 0) -> list:
+    """csrc/p256.h's field arithmetic as compiled for `device` (P256_HOST: for the host), over
+    lists of integers below the modulus: op in P256_OPS, field "p" or "n" (include/
+    nzcb_internal.h nzcb_debug_p256_field). Returns the list of results."""
+    b = a if b is None else b
+    if len(a) != len(b):
+        raise ValueError("operand lists differ in length")
+    ab = b"".join(int(x).to_bytes(32, "big") for x in a)
+    bb = b"".join(int(x).to_bytes(32, "big") for x in b)
+    out = _out(32 * len(a))
+    err = _Err()
+    _check(load().nzcb_debug_p256_field(device, P256_OPS[op], {"p": 0, "n": 1}[field], ab, bb, len(a), out,
+                                        ctypes.byref(err)), err)
+    raw = bytes(out)
+    return [int.from_bytes(raw[32 * i:32 * i + 32], "big") for i in range(len(a))]
+
+
+class P256Key:
+    """An ECDSA P-256 public key with its fixed-base tables resident on the GPU, and batch
+    verification of SHA-256 digests against r || s signatures (include/nzcb.h nzcb_p256_*; COSE
+    ES256, the signature of an NZ COVID Pass). The key is (x, y) as integers or 32-byte
+    big-endian strings, 64 bytes x || y, or a JWK / DID-document dict with base64url "x" and "y".
+    device = P256_HOST (-1) builds the tables and verifies on the host. Whether the key is the
+    issuer's is the caller's business. window: the tables' window width, 4 or 8 (0: the
+    library's default; include/nzcb_internal.h); the statuses do not depend on it."""
+
+    def __init__(self, x, y=None, device: int = 0, window: int = 0):
+        if isinstance(x, dict):
+            xy = _b64url(x["x"]) + _b64url(x["y"])
+        elif y is None:
+            xy = bytes(x)
+        else:
+            xy = b"".join(v.to_bytes(32, "big") if isinstance(v, int) else bytes(v) for v in (x, y))
+        if len(xy) != 64:
+            raise ValueError("a P-256 public key is 32 + 32 bytes")
+        self.lib = load()
+        self.device = device
+        self.xy = xy
+        err = _Err()
+        if window:
+            self.h = self.lib.nzcb_engine_p256_key_create(xy, device, window, ctypes.byref(err))
+        else:
+            self.h = self.lib.nzcb_p256_key_create(xy, device, ctypes.byref(err))
+        if not self.h:
+            raise NzcbError(err.code, err.msg.decode(errors="replace"))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.nzcb_p256_key_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def _verify(self, hashes, hash_stride: int, sigs, sig_stride: int, count: int, on_device: bool,
+                stream=None) -> list:
+        st = (ctypes.c_int32 * max(count, 1))()
+        err = _Err()
+        _check(self.lib.nzcb_p256_verify(self.h, hashes, hash_stride, sigs, sig_stride, count, int(on_device), st,
+                                         stream, ctypes.byref(err)), err)
+        return [st[i] for i in range(count)]
+
+    def verify(self, hashes, sigs, hash_stride: int = 32, sig_stride: int = 64) -> list:
+        """hashes: 32-byte digests, sigs: 64-byte r || s, each a list of byte strings or one
+        buffer with item i at i * stride. Returns one SIG_OK / SIG_INVALID / SIG_RANGE each."""
+        if isinstance(hashes, (list, tuple)):
+            if any(len(h) != 32 for h in hashes):
+                raise ValueError("a hash is 32 bytes")
+            hashes, hash_stride = b"".join(hashes), 32
+        if isinstance(sigs, (list, tuple)):
+            if any(len(s) != 64 for s in sigs):
+                raise ValueError("a signature is 64 bytes (r || s)")
+            sigs, sig_stride = b"".join(sigs), 64
+        hashes, sigs = bytes(hashes), bytes(sigs)
+        if hash_stride < 32 or sig_stride < 64:
+            raise ValueError("strides are at least 32 and 64")
+        def items(buf, stride, size, what):
+            if stride == size and len(buf) % size:
+                raise ValueError(f"the {what} are not whole {size}-byte items")
+            return (len(buf) + stride - size) // stride if len(buf) >= size else 0
+
+        count = items(hashes, hash_stride, 32, "hashes")
+        if items(sigs, sig_stride, 64, "signatures") != count or (not count and (hashes or sigs)):
+            raise ValueError("the signatures do not match the hashes")
+        return self._verify(hashes, hash_stride, sigs, sig_stride, count, False)
+
+    def verify_dev(self, dev_hashes: int, hash_stride: int, dev_sigs: int, sig_stride: int, count: int,
+                   stream: int | None = None) -> list:
+        """The same over HBM buffers on the key's device, read in place (pointers and strides
+        multiples of 4). The buffers must be complete when the call starts, or their producer
+        enqueued on `stream` (a HIP stream handle) before it: without one the call runs on a
+        stream of its own, which waits for no other stream."""
+        return self._verify(c_void_p(dev_hashes), hash_stride, c_void_p(dev_sigs), sig_stride, count, True, stream)
+
+    def verify_records(self, dev_records: int, dev_sigs: int, count: int, stream: int | None = None) -> list:
+        """`count` nzcb_nzcp_record in HBM, as nzcp_witness_dev wrote them: record i's tbs_sha256
+        against the 64-byte signature at dev_sigs + 64 i. nzcp_witness_dev is asynchronous: pass
+        the stream it ran on, or synchronise first (see verify_dev)."""
+        return self.verify_dev(dev_records + NzcpRecord.tbs_sha256.offset, ctypes.sizeof(NzcpRecord), dev_sigs, 64,
+                               count, stream)
+
+    def verify_passes(self, uris) -> list:
+        """Pass URIs -> one dict each: valid, status (SIG_*, or None when the pass was not sent
+        to the verifier), reason (None when valid), alg, kid, iss, nbf, exp. The Sig_structure is
+        hashed on the host; an alg other than -7 (ES256), a signature that is not 64 bytes or a
+        pass that does not decode is reported with its reason and not verified."""
+        import hashlib
+        from . import nzcp
+        out, hashes, sigs, sent = [], [], [], []
+        for uri in uris:
+            d = {"valid": False, "status": None, "reason": None, "alg": None, "kid": None, "iss": None,
+                 "nbf": None, "exp": None}
+            out.append(d)
+            try:
+                protected, payload, sig = nzcp.decode_pass(uri)
+                hdr = nzcp.protected_header(uri)
+                claims, _ = nzcp.cbor_decode(payload)
+                d.update(alg=hdr.get(1), kid=hdr.get(4), iss=claims.get(1), nbf=claims.get(5), exp=claims.get(4))
+            except Exception as e:  # noqa: BLE001  (any malformed pass is a verdict, not a failure of the batch)
+                d["reason"] = f"malformed pass: {e}"
+                continue
+            if d["alg"] != -7:
+                d["reason"] = f"unsupported alg {d['alg']} (ES256 is -7)"
+            elif not isinstance(sig, bytes) or len(sig) != 64:
+                d["reason"] = "signature is not 64 bytes"
+            else:
+                hashes.append(hashlib.sha256(nzcp.sig_structure(protected, payload)).digest())
+                sigs.append(sig)
+                sent.append(d)
+        for d, st in zip(sent, self.verify(hashes, sigs) if sent else []):
+            d["status"] = st
+            d["valid"] = st == SIG_OK
+            d["reason"] = None if st == SIG_OK else ("invalid signature" if st == SIG_INVALID
+                                                      else "signature out of range")
+        return out
+
+    def mul2(self, u1, u2) -> list:
+        """u1[i] G + u2[i] Q through the verifier's table code (include/nzcb_internal.h
+        nzcb_debug_p256_mul2): affine (x, y) integer pairs, None for the point at infinity."""
+        if len(u1) != len(u2):
+            raise ValueError("scalar lists differ in length")
+        a = b"".join(int(v).to_bytes(32, "big") for v in u1)
+        b = b"".join(int(v).to_bytes(32, "big") for v in u2)
+        out = _out(64 * len(u1))
+        err = _Err()
+        _check(self.lib.nzcb_debug_p256_mul2(self.h, a, b, len(u1), out, ctypes.byref(err)), err)
+        raw = bytes(out)
+        pts = []
+        for i in range(len(u1)):
+            x, y = int.from_bytes(raw[64 * i:64 * i + 32], "big"), int.from_bytes(raw[64 * i + 32:64 * i + 64], "big")
+            pts.append(None if x == 0 and y == 0 else (x, y))
+        return pts
+
+    @staticmethod
+    def timings() -> list:
+        """Milliseconds of this thread's last calls: table build, verify kernel, verify call."""
+        ms = (c_double * 3)()
+        n = load().nzcb_debug_p256_timings(ms, 3)
         return list(ms)[:n]
 
 

@@ -36,6 +36,11 @@ EXAMPLE_PASS_URI = (  # /root/reference/test/nzcp.js:71 (MoH example pass)
     "WY6KOMFWWKZ2TOBQXE4TPO5RWI33CNIYTSNRQFUYDILJRGYDVAYFE6VGU4MCDGK7DHLLYWHVPUS2YIDJOA6Y524TD3AZRM263WTY2BE4"
     "DPKIF27WKF3UDNNVSVWRDYIYVJ65IRJJJ6Z25M2DO4YZLBHWFQGVQR5ZLIWEQJOZTS3IQ7JTNCFDX")
 
+# The NZCP specification's example issuer key "key-1" (JWK coordinates, base64url), under which
+# EXAMPLE_PASS_URI verifies. The live key is not here: callers supply the keys they trust.
+EXAMPLE_PUBLIC_KEY = {"kty": "EC", "crv": "P-256", "x": "zRR-XGsCp12Vvbgui4DD6O6cqmhfPuXMhi1OxPl8760",
+                      "y": "Iv5SU6FuW-TRYh5_GOrJlcV_gpF_GpFQhCOD8LSk3T0"}
+
 EXAMPLE_KID = b"key-1"
 LIVE_KID = b"z12Kf7UQ"
 EXAMPLE_ISS = "did:web:nzcp.covid19.health.nz"
@@ -155,6 +160,14 @@ def decode_pass(pass_uri: str):
         raise ValueError("not a COSE_Sign1 structure")
     protected, _unprotected, payload, signature = cose.value
     return protected, payload, signature
+
+
+def protected_header(pass_uri: str) -> dict:
+    """The COSE protected header map of a pass: {1: alg (-7 = ES256), 4: kid}."""
+    hdr, _ = cbor_decode(decode_pass(pass_uri)[0])
+    if not isinstance(hdr, dict):
+        raise ValueError("the protected header is not a map")
+    return hdr
 
 
 def sig_structure(protected: bytes, payload: bytes) -> bytes:
