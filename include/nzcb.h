@@ -408,6 +408,104 @@ int nzcb_p256_verify(nzcb_p256_key* k, const void* hashes, size_t hash_stride, c
                      int count, int on_device, int32_t* status_out, void* stream, nzcb_err* err);
 void nzcb_p256_key_destroy(nzcb_p256_key* k);
 
+/* ---- Pass decode (NZCP:/<version>/<base32> -> COSE_Sign1 -> digest and circuit inputs) ---- */
+/* What a holder presents is the URI. nzcb_nzcp_decode takes batches of them, one GPU workgroup
+ * per pass (csrc/nzcp_decode.hip; the functions themselves are csrc/nzcp_decode.h, the same on
+ * both paths, device = NZCB_NZCP_HOST runs them in a host loop), and leaves per pass a fixed-size
+ * record, the SHA-256 of the COSE Sig_structure where nzcb_p256_verify reads it in place, and the
+ * main's input signals where nzcb_nzcp_witness_dev / nzcb_wprog_run_dev read them. The input is
+ * untrusted: no step reads outside the URI, the decoded COSE bytes or the item it is parsing, and
+ * every length taken from the input is compared in 64 bits against the bytes left before it is
+ * used. Steps, in this order; the first failing one sets status and detail and ends the pass:
+ *   LENGTH    the URI is longer than NZCB_PASS_MAX_URI bytes (detail = its length)
+ *   PREFIX    not "NZCP:/", one to nine decimal digits (version: reported, not judged), "/" and
+ *             at least one more byte
+ *   BASE32    a byte of the rest outside A-Z2-7 (detail = the lowest such index in the URI); no
+ *             padding, no lower case. The COSE bytes are the floor(5 L / 8) whole bytes.
+ *   CBOR heads, definite lengths only, shortest form not required: additional info 28..31 (the
+ *             break byte included) gives CBOR; a head, a string body or an array / map item
+ *             count that exceeds the bytes left of the region being parsed gives TRUNCATED
+ *             (detail of both = the head's offset in the COSE bytes). Values that are not looked
+ *             at are skipped with a counter of items still to read: any nesting depth, no stack.
+ *   NOT_COSE  not tag 18 around an array of 4, or item 0 (protected header) or item 2 (payload)
+ *             is not a byte string (detail = the offending head). Item 1 is skipped. Item 3: a
+ *             byte string gives sig_len and, when it is 64 bytes, sig; anything else is skipped
+ *             and NZCB_PASS_HAS_SIG stays clear. Bytes after the COSE item are ignored.
+ *   HEADER    the protected bytes do not begin with a map. Key 1 with an integer value: alg
+ *             (saturated to int32); key 4 with a byte string: kid.
+ *   CLAIMS    the payload does not begin with a map. Key 1 with a text value: iss; 4 and 5 with
+ *             unsigned values: exp, nbf; 7 with a byte string: cti. In both maps everything else
+ *             is skipped, a repeated key's last occurrence counts, and a known key whose value
+ *             has another type is absent. Both are parsed within their own byte string only.
+ * Then ToBeSigned = 84 6a "Signature1" bstr(protected) 40 bstr(payload) with shortest heads,
+ * tbs_len and tbs_sha256. On status != OK every field but status, detail and version is zero
+ * (version is set once PREFIX has passed). */
+#define NZCB_PASS_MAX_URI 2048
+#define NZCB_NZCP_HOST (-1)
+enum {
+  NZCB_PASS_OK = 0,
+  NZCB_PASS_ERR_LENGTH = 1,
+  NZCB_PASS_ERR_PREFIX = 2,
+  NZCB_PASS_ERR_BASE32 = 3,
+  NZCB_PASS_ERR_TRUNCATED = 4,
+  NZCB_PASS_ERR_CBOR = 5,
+  NZCB_PASS_ERR_NOT_COSE = 6,
+  NZCB_PASS_ERR_HEADER = 7,
+  NZCB_PASS_ERR_CLAIMS = 8
+};
+enum {
+  NZCB_PASS_HAS_ALG = 1,
+  NZCB_PASS_HAS_KID = 2,
+  NZCB_PASS_HAS_ISS = 4,
+  NZCB_PASS_HAS_NBF = 8,
+  NZCB_PASS_HAS_EXP = 16,
+  NZCB_PASS_HAS_CTI = 32,
+  NZCB_PASS_HAS_SIG = 64
+};
+typedef struct nzcb_nzcp_pass {
+  int32_t status;          /* NZCB_PASS_* */
+  uint32_t detail;
+  uint32_t version;
+  uint32_t present;        /* NZCB_PASS_HAS_* */
+  int32_t alg;             /* -7 = ES256 */
+  uint32_t kid_len, iss_len, cti_len, sig_len; /* true lengths; the arrays hold the first bytes */
+  uint32_t cose_len;       /* COSE bytes consumed */
+  uint32_t protected_off, protected_len, payload_off, payload_len; /* within the COSE bytes */
+  uint32_t tbs_len;
+  uint32_t fits;           /* 1: the pass's input block is filled */
+  uint64_t nbf, exp;
+  uint8_t kid[32];
+  uint8_t cti[32];
+  uint8_t iss[64];
+  uint8_t sig[64];         /* r || s when sig_len = 64, zeros otherwise */
+  uint8_t tbs_sha256[32];
+} nzcb_nzcp_pass;
+/* out = {sizeof(nzcb_nzcp_pass), offsetof sig, offsetof tbs_sha256}: both offsets are multiples
+ * of 4 and the size of 8, so nzcb_p256_verify(k, recs + out[2], out[0], recs + out[1], out[0],
+ * count, on_device = 1, ...) verifies a record array in place. */
+void nzcb_nzcp_pass_layout(uint32_t out[3]);
+/* Host buffers. uris: the URIs' bytes back to back, URI i = [offsets[i], offsets[i + 1]);
+ * offsets: count + 1 values, non-decreasing, the last at most 2^31 (NZCB_ERR_ARG otherwise).
+ * prm: the circuit whose inputs to build (only max_tbs_bytes counts), NULL = none. data20: count
+ * x 20 pass-through bytes, NULL = zeros. passes_out: count records. inputs_out (may be NULL, needs
+ * prm): count x nzcb_nzcp_input_signals(prm) x 32 bytes; pass i's block is the main's input
+ * signals (toBeSigned bits, toBeSignedLen, data bits after the reversed-bytes / reversed-bits
+ * rearrangement) when status = OK and tbs_len <= max_tbs_bytes (fits = 1), all zero bytes
+ * otherwise (fits = 0). tbs_out (may be NULL): pass i's first min(tbs_len, tbs_stride) ToBeSigned
+ * bytes at tbs_out + i * tbs_stride, zeros after them. Returns 0 whatever the verdicts (count = 0
+ * is fine); the records do not depend on the batch, its order or the path. */
+int nzcb_nzcp_decode(int device, const uint8_t* uris, const uint32_t* offsets, int count,
+                     const nzcb_nzcp_params* prm, const uint8_t* data20, nzcb_nzcp_pass* passes_out,
+                     uint8_t* inputs_out, uint8_t* tbs_out, size_t tbs_stride, nzcb_err* err);
+/* The same over HBM buffers on `device`, asynchronous on `stream` (a hipStream_t, NULL = the
+ * default stream) like nzcb_nzcp_witness_dev: work enqueued on the stream afterwards sees the
+ * results. dev_passes is a multiple of 8, dev_inputs of 16. dev_offsets is read back once, ordered on
+ * the stream, to validate it before the kernel is enqueued: the call waits for the stream's earlier
+ * work, not for its own kernel. */
+int nzcb_nzcp_decode_dev(int device, const void* dev_uris, const void* dev_offsets, int count,
+                         const nzcb_nzcp_params* prm, const void* dev_data20, void* dev_passes, void* dev_inputs,
+                         void* dev_tbs, size_t tbs_stride, void* stream, nzcb_err* err);
+
 /* ---- Setup ------------------------------------------ */
 /* snarkjs `plonk setup <r1cs> <ptau> <zkey>` (snarkjs 0.4.12 plonk_setup.js, run at
  * /root/reference/Makefile:55,60): iden3 r1cs + powers-of-tau file -> snarkjs-0.4 PLONK

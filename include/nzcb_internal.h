@@ -195,6 +195,10 @@ int nzcb_debug_p256_mul2(nzcb_p256_key* k, const uint8_t* u1, const uint8_t* u2,
  * number of values written (cap <= 3). */
 int nzcb_debug_p256_timings(double* ms, int cap);
 
+/* ---- Pass decode (csrc/nzcp_decode.h, csrc/nzcp_decode.hip) ----------------------------- */
+/* Milliseconds of the calling thread's last nzcb_nzcp_decode: [0] the decode kernel (HIP events;
+ * 0 on the host path), [1] the call's wall time. Returns the number of values written (cap <= 2). */
+int nzcb_debug_nzcp_decode_timings(double* ms, int cap);
 
 #ifdef __cplusplus
 }

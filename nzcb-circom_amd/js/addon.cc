@@ -873,6 +873,152 @@ napi_value P256Verify(napi_env env, napi_callback_info info) {
   return promise;
 }
 
+// one nzcpDecode call on a worker thread: the URIs decoded (nzcb_nzcp_decode, on the GPU or with
+// device -1 on the host) and, when a key came with them, each record's digest checked against
+// its signature (nzcb_p256_verify reading both out of the record array by stride). The inputs are
+// copied; the promise is settled on the main thread.
+struct NzcpDecodeWork {
+  napi_deferred deferred = nullptr;
+  napi_async_work work = nullptr;
+  std::vector<uint8_t> uris, data, records, inputs;
+  std::vector<uint32_t> offsets;
+  std::vector<int32_t> status;
+  nzcb_nzcp_params prm{};
+  bool has_prm = false, has_key = false;
+  uint8_t key[64];
+  int device = 0;
+  int rc = 0;
+  nzcb_err err{};
+};
+
+void nzcp_decode_execute(napi_env, void* data) {
+  NzcpDecodeWork* w = static_cast<NzcpDecodeWork*>(data);
+  const int count = (int)w->offsets.size() - 1;
+  uint32_t lay[3];
+  nzcb_nzcp_pass_layout(lay);
+  w->records.assign((size_t)lay[0] * count, 0);
+  if (w->has_prm) w->inputs.assign(nzcb_nzcp_input_signals(&w->prm) * 32 * (size_t)count, 0);
+  w->rc = nzcb_nzcp_decode(w->device, w->uris.data(), w->offsets.data(), count, w->has_prm ? &w->prm : nullptr,
+                           w->data.empty() ? nullptr : w->data.data(),
+                           reinterpret_cast<nzcb_nzcp_pass*>(w->records.data()),
+                           w->has_prm ? w->inputs.data() : nullptr, nullptr, 0, &w->err);
+  if (w->rc || !w->has_key || !count) return;
+  nzcb_p256_key* k = nzcb_p256_key_create(w->key, w->device, &w->err);
+  if (!k) {
+    w->rc = w->err.code ? w->err.code : NZCB_ERR_INTERNAL;
+    return;
+  }
+  w->status.assign(count, NZCB_SIG_INVALID);
+  w->rc = nzcb_p256_verify(k, w->records.data() + lay[2], lay[0], w->records.data() + lay[1], lay[0], count, 0,
+                           w->status.data(), nullptr, &w->err);
+  nzcb_p256_key_destroy(k);
+}
+
+void nzcp_decode_complete(napi_env env, napi_status status, void* data) {
+  NzcpDecodeWork* w = static_cast<NzcpDecodeWork*>(data);
+  if (status != napi_ok || w->rc != 0) {
+    napi_reject_deferred(env, w->deferred,
+                         make_error(env, w->rc ? w->err.code : NZCB_ERR_INTERNAL,
+                                    w->rc ? w->err.msg : "nzcpDecode: the work was cancelled"));
+  } else {
+    napi_value out, v;
+    napi_create_object(env, &out);
+    napi_create_buffer_copy(env, w->records.size(), w->records.data(), nullptr, &v);
+    napi_set_named_property(env, out, "records", v);
+    if (w->has_prm) {
+      napi_create_buffer_copy(env, w->inputs.size(), w->inputs.data(), nullptr, &v);
+      napi_set_named_property(env, out, "inputs", v);
+    }
+    if (w->has_key) {
+      napi_create_array_with_length(env, w->status.size(), &v);
+      for (size_t i = 0; i < w->status.size(); i++) {
+        napi_value x;
+        napi_create_int32(env, w->status[i], &x);
+        napi_set_element(env, v, (uint32_t)i, x);
+      }
+      napi_set_named_property(env, out, "status", v);
+    }
+    napi_resolve_deferred(env, w->deferred, out);
+  }
+  napi_delete_async_work(env, w->work);
+  delete w;
+}
+
+// nzcpDecode(uris: Buffer (the URIs back to back), offsets: Buffer (count + 1 u32 LE), maxTbsBytes:
+//            number (0 = no circuit inputs), data: Buffer (20 count) | null, device: number,
+//            key: Buffer (64) | null)
+//   -> Promise<{records: Buffer (count nzcb_nzcp_pass), inputs?: Buffer, status?: number[count]}>
+napi_value NzcpDecode(napi_env env, napi_callback_info info) {
+  size_t argc = 6;
+  napi_value argv[6];
+  CHECK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  const uint8_t *ub = nullptr, *ob = nullptr, *db = nullptr, *kb = nullptr;
+  size_t ul = 0, ol = 0, dl = 0, kl = 0;
+  int32_t max_tbs = 0, device = 0;
+  const char* usage = "nzcpDecode(uris: Buffer, offsets: Buffer(4 (n + 1)), maxTbsBytes, data: Buffer(20 n) | null, "
+                      "device, key: Buffer(64) | null)";
+  if (argc < 6 || !buf_arg(env, argv[0], &ub, &ul) || !buf_arg(env, argv[1], &ob, &ol) || ol < 4 || ol % 4 ||
+      napi_get_value_int32(env, argv[2], &max_tbs) != napi_ok ||
+      napi_get_value_int32(env, argv[4], &device) != napi_ok) {
+    napi_throw_type_error(env, nullptr, usage);
+    return nullptr;
+  }
+  const size_t count = ol / 4 - 1;
+  // null stands for "none": only a Buffer may go to napi_get_buffer_info
+  auto optional = [&](napi_value v, const uint8_t** p, size_t* l) {
+    bool is = false;
+    return napi_is_buffer(env, v, &is) == napi_ok && is && buf_arg(env, v, p, l);
+  };
+  const bool has_data = optional(argv[3], &db, &dl), has_key = optional(argv[5], &kb, &kl);
+  if ((has_data && dl != 20 * count) || (has_key && kl != 64) || count > 0x7fffffffu) {
+    napi_throw_type_error(env, nullptr, usage);
+    return nullptr;
+  }
+  NzcpDecodeWork* w = new NzcpDecodeWork();
+  w->uris.assign(ub, ub + ul);
+  w->offsets.resize(count + 1);
+  memcpy(w->offsets.data(), ob, ol);  // little-endian hosts only, as the rest of the addon
+  if (w->offsets[count] > ul) {       // the C ABI trusts the offsets to lie within the buffer
+    delete w;
+    napi_throw_range_error(env, nullptr, "nzcpDecode: the offsets run past the URI bytes");
+    return nullptr;
+  }
+  if (has_data) w->data.assign(db, db + dl);
+  if (max_tbs) {
+    w->has_prm = true;
+    w->prm.max_tbs_bytes = max_tbs;
+  }
+  if (has_key) {
+    w->has_key = true;
+    memcpy(w->key, kb, 64);
+  }
+  w->device = device;
+  napi_value promise, name;
+  if (napi_create_promise(env, &w->deferred, &promise) != napi_ok ||
+      napi_create_string_utf8(env, "nzcb.nzcpDecode", NAPI_AUTO_LENGTH, &name) != napi_ok ||
+      napi_create_async_work(env, nullptr, name, nzcp_decode_execute, nzcp_decode_complete, w, &w->work) != napi_ok ||
+      napi_queue_async_work(env, w->work) != napi_ok) {
+    delete w;
+    napi_throw_error(env, nullptr, "nzcb addon: N-API call failed");
+    return nullptr;
+  }
+  return promise;
+}
+
+// nzcpPassLayout() -> [sizeof(nzcb_nzcp_pass), offsetof sig, offsetof tbs_sha256]
+napi_value NzcpPassLayout(napi_env env, napi_callback_info) {
+  uint32_t lay[3];
+  nzcb_nzcp_pass_layout(lay);
+  napi_value arr;
+  CHECK(napi_create_array_with_length(env, 3, &arr));
+  for (uint32_t i = 0; i < 3; i++) {
+    napi_value x;
+    CHECK(napi_create_uint32(env, lay[i], &x));
+    CHECK(napi_set_element(env, arr, i, x));
+  }
+  return arr;
+}
+
 // r1csInfo(path: string) -> number[8] (nzcb_r1cs_info; parsed on the host, no GPU)
 napi_value R1csInfo(napi_env env, napi_callback_info info) {
   size_t argc = 1;
@@ -1033,6 +1179,8 @@ napi_value Init(napi_env env, napi_value exports) {
       {"wtnsCheck", nullptr, WtnsCheck, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"r1csInfo", nullptr, R1csInfo, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"p256Verify", nullptr, P256Verify, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"nzcpDecode", nullptr, NzcpDecode, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"nzcpPassLayout", nullptr, NzcpPassLayout, nullptr, nullptr, nullptr, napi_default, nullptr},
   };
   napi_define_properties(env, exports, sizeof(props) / sizeof(props[0]), props);
   return exports;

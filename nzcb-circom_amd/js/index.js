@@ -605,8 +605,128 @@ async function p256Verify(key, hashes, sigs, options) {
     options.device === undefined ? 0 : options.device);
 }
 
+// Pass decode (include/nzcb.h nzcb_nzcp_decode): URIs -> records, on the GPU (options.device,
+// default 0) or on the host (-1), on a worker thread. options.circuit 'live' | 'example' adds
+// `inputs`: one Buffer, pass i's input signals (32-byte LE each, what wtns.calculate's programs
+// and nzcp.witness take) at i * (8 max + 161) * 32, zeros where the record's fits is 0;
+// options.data: the 20 pass-through bytes, one Buffer for all passes or one per pass.
+// Resolves to {records, inputs?}; a record's absent fields are null.
+const PASS_STATUS = ['OK', 'LENGTH', 'PREFIX', 'BASE32', 'TRUNCATED', 'CBOR', 'NOT_COSE', 'HEADER', 'CLAIMS'];
+const PASS_BYTES = 304;
+{
+  const lay = addon.nzcpPassLayout();
+  if (lay[0] !== PASS_BYTES || lay[1] !== 208 || lay[2] !== 272) {
+    throw new Error(`nzcb: nzcb_nzcp_pass is laid out as ${lay}, index.js expects 304,208,272`);
+  }
+}
+
+function passRecord(r) {
+  const present = r.readUInt32LE(12);
+  const u64 = (off) => {
+    const v = r.readBigUInt64LE(off);
+    return v <= BigInt(Number.MAX_SAFE_INTEGER) ? Number(v) : v;
+  };
+  const first = (off, cap, len) => Buffer.from(r.subarray(off, off + Math.min(cap, len)));
+  const status = r.readInt32LE(0);
+  return {
+    status,
+    statusName: PASS_STATUS[status],
+    detail: r.readUInt32LE(4),
+    version: r.readUInt32LE(8),
+    alg: present & 1 ? r.readInt32LE(16) : null,
+    kid: present & 2 ? first(80, 32, r.readUInt32LE(20)).toString('utf8') : null,
+    kidLen: r.readUInt32LE(20),
+    iss: present & 4 ? first(144, 64, r.readUInt32LE(24)).toString('utf8') : null,
+    issLen: r.readUInt32LE(24),
+    nbf: present & 8 ? u64(64) : null,
+    exp: present & 16 ? u64(72) : null,
+    cti: present & 32 ? first(112, 32, r.readUInt32LE(28)) : null,
+    ctiLen: r.readUInt32LE(28),
+    sig: present & 64 ? first(208, 64, 64) : null,
+    sigLen: r.readUInt32LE(32),
+    coseLen: r.readUInt32LE(36),
+    protectedOff: r.readUInt32LE(40),
+    protectedLen: r.readUInt32LE(44),
+    payloadOff: r.readUInt32LE(48),
+    payloadLen: r.readUInt32LE(52),
+    toBeSignedLen: r.readUInt32LE(56),
+    fits: r.readUInt32LE(60) !== 0,
+    toBeSignedHash: r.subarray(272, 304).toString('hex'),
+  };
+}
+
+async function decodeRaw(uris, options, key) {
+  const bufs = uris.map((u) => (Buffer.isBuffer(u) ? u : Buffer.from(String(u), 'utf8')));
+  const offsets = Buffer.alloc(4 * (bufs.length + 1));
+  let at = 0;
+  bufs.forEach((b, i) => {
+    at += b.length;
+    if (at > 0x80000000) throw new Error('more than 2^31 bytes of URIs');
+    offsets.writeUInt32LE(at, 4 * (i + 1));
+  });
+  let maxTbs = 0;
+  if (options.circuit !== undefined) {
+    if (!NZCP_PARAMS[options.circuit]) throw new Error("options.circuit is 'live' or 'example'");
+    maxTbs = NZCP_PARAMS[options.circuit][1];
+  }
+  let data = null;
+  if (options.data !== undefined && options.data !== null) {
+    data = Array.isArray(options.data) ? Buffer.concat(options.data.map((d) => Buffer.from(d)))
+      : Buffer.from(options.data);
+    if (data.length === 20 && bufs.length !== 1) data = Buffer.concat(bufs.map(() => data));
+    if (data.length !== 20 * bufs.length) throw new Error('data must be 20 bytes, or 20 bytes per pass');
+  }
+  const raw = await addon.nzcpDecode(Buffer.concat(bufs), offsets, maxTbs, data,
+    options.device === undefined ? 0 : options.device, key || null);
+  raw.passes = bufs.map((_, i) => passRecord(raw.records.subarray(i * PASS_BYTES, (i + 1) * PASS_BYTES)));
+  return raw;
+}
+
+async function decodePasses(uris, options) {
+  options = options || {};
+  const raw = await decodeRaw(uris, options, null);
+  const out = { records: raw.passes };
+  if (raw.inputs) out.inputs = raw.inputs;
+  return out;
+}
+
+// verifyPasses with options.decode = 'device': the URIs go to the library as they are, are decoded
+// there (on options.device, or on the host with -1) and each record's digest is checked against
+// its signature; no per-pass decoding or hashing in JavaScript. Same objects and reason texts as
+// the default route, except "malformed pass: <status name> at <detail>"; a record keeps the
+// first 32 bytes of a kid and 64 of an iss.
+async function verifyPassesDecoded(uris, options) {
+  const raw = await decodeRaw(uris, { device: options.device }, p256KeyBuffer(options.key));
+  return raw.passes.map((r, i) => {
+    const d = { valid: false, status: null, reason: null, alg: null, kid: null, iss: null, nbf: null, exp: null };
+    if (r.status !== 0) {
+      d.reason = `malformed pass: ${r.statusName} at ${r.detail}`;
+      return d;
+    }
+    Object.assign(d, { alg: r.alg, kid: r.kid, iss: r.iss, nbf: r.nbf, exp: r.exp });
+    if (options.now !== undefined) {
+      d.expired = typeof d.exp === 'number' && options.now >= d.exp;
+      d.notYetValid = typeof d.nbf === 'number' && options.now < d.nbf;
+    }
+    if (d.alg !== -7) {
+      d.reason = `unsupported alg ${d.alg} (ES256 is -7)`;
+    } else if (r.sig === null || r.sigLen !== 64) {
+      d.reason = 'signature is not 64 bytes';
+    } else {
+      d.status = raw.status[i];
+      d.valid = d.status === 0;
+      d.reason = SIG_REASON[d.status];
+    }
+    return d;
+  });
+}
+
 async function verifyPasses(uris, options) {
   options = options || {};
+  if (options.decode !== undefined) {
+    if (options.decode !== 'device') throw new Error("options.decode is 'device' or left out");
+    return verifyPassesDecoded(uris, options);
+  }
   const key = p256KeyBuffer(options.key);
   const out = [];
   const sent = [];
@@ -658,7 +778,7 @@ async function verifyPass(uri, options) {
 module.exports = {
   plonk: { setup, prove, fullProve, verify, verifyBatch, exportSolidityCallData },
   zKey: { exportVerificationKey, exportSolidityVerifier },
-  nzcp: Object.assign({}, nzcpHost, { witness: nzcpWitness, verifyPass, verifyPasses, p256Verify }),
+  nzcp: Object.assign({}, nzcpHost, { witness: nzcpWitness, verifyPass, verifyPasses, p256Verify, decodePasses }),
   wtns: { calculate: wtnsCalculate, remapProgram, check: wtnsCheck },
   r1cs: { info: r1csInfo },
   version: addon.version,

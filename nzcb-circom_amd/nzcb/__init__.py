@@ -51,6 +51,7 @@ EXPORTED_SYMBOLS = [
     "nzcb_engine_r1cs_create", "nzcb_debug_r1cs_check_timings",
     "nzcb_p256_key_create", "nzcb_p256_verify", "nzcb_p256_key_destroy", "nzcb_engine_p256_key_create",
     "nzcb_debug_p256_field", "nzcb_debug_p256_mul2", "nzcb_debug_p256_timings",
+    "nzcb_nzcp_pass_layout", "nzcb_nzcp_decode", "nzcb_nzcp_decode_dev", "nzcb_debug_nzcp_decode_timings",
 ]
 
 NZCB_FAULT_QUOTIENT = 1  # include/nzcb_internal.h
@@ -61,6 +62,12 @@ R1CS_HOST = -1  # include/nzcb.h NZCB_R1CS_HOST: the witness check on the host
 WITNESS_WTNS, WITNESS_HOST, WITNESS_DEVICE = 0, 1, 2  # include/nzcb.h NZCB_WITNESS_*
 P256_HOST = -1  # include/nzcb.h NZCB_P256_HOST: signature verification on the host
 SIG_OK, SIG_INVALID, SIG_RANGE = 0, 1, 2  # include/nzcb.h NZCB_SIG_*
+NZCP_HOST = -1  # include/nzcb.h NZCB_NZCP_HOST: the pass decode on the host
+PASS_MAX_URI = 2048  # include/nzcb.h NZCB_PASS_MAX_URI
+PASS_STATUS_NAMES = ("OK", "LENGTH", "PREFIX", "BASE32", "TRUNCATED", "CBOR", "NOT_COSE", "HEADER",
+                     "CLAIMS")  # include/nzcb.h NZCB_PASS_*
+PASS_HAS_ALG, PASS_HAS_KID, PASS_HAS_ISS, PASS_HAS_NBF, PASS_HAS_EXP, PASS_HAS_CTI, PASS_HAS_SIG = (
+    1, 2, 4, 8, 16, 32, 64)  # include/nzcb.h NZCB_PASS_HAS_*
 P256_OPS = {"add": 0, "sub": 1, "mul": 2, "sqr": 3, "inv": 4}  # include/nzcb_internal.h NZCB_P256_OP_*
 
 
@@ -132,6 +139,17 @@ class NzcpRecord(ctypes.Structure):
                 ("pub", (c_uint8 * 32) * 3)]
 
 
+class NzcpPass(ctypes.Structure):
+    """include/nzcb.h nzcb_nzcp_pass; load() asserts the layout against nzcb_nzcp_pass_layout."""
+    _fields_ = [("status", ctypes.c_int32), ("detail", c_uint32), ("version", c_uint32), ("present", c_uint32),
+                ("alg", ctypes.c_int32), ("kid_len", c_uint32), ("iss_len", c_uint32), ("cti_len", c_uint32),
+                ("sig_len", c_uint32), ("cose_len", c_uint32), ("protected_off", c_uint32),
+                ("protected_len", c_uint32), ("payload_off", c_uint32), ("payload_len", c_uint32),
+                ("tbs_len", c_uint32), ("fits", c_uint32), ("nbf", c_uint64), ("exp", c_uint64),
+                ("kid", c_uint8 * 32), ("cti", c_uint8 * 32), ("iss", c_uint8 * 64), ("sig", c_uint8 * 64),
+                ("tbs_sha256", c_uint8 * 32)]
+
+
 # circuits/nzcp_live.circom / nzcp_example.circom mains
 NZCP_LIVE = dict(is_live=1, max_tbs_bytes=351, max_array_len_vc=0, max_map_len_vc=4)
 NZCP_EXAMPLE = dict(is_live=0, max_tbs_bytes=314, max_array_len_vc=0, max_map_len_vc=4)
@@ -200,6 +218,7 @@ def load(path: str | None = None):
         "nzcb_engine_ntt": (c_int, [c_void_p, u8p, u8p, c_int, c_int, POINTER(_Err)]),
         "nzcb_engine_msm": (c_int, [c_void_p, u8p, u8p, c_size_t, c_int, u8p, POINTER(_Err)]),
         "nzcb_dev_alloc": (c_void_p, [c_size_t]),
+        "nzcb_dev_alloc_on": (c_void_p, [c_int, c_size_t]),
         "nzcb_dev_free": (None, [c_void_p]),
         "nzcb_memcpy_h2d": (c_int, [c_void_p, c_void_p, c_size_t]),
         "nzcb_memcpy_d2h": (c_int, [c_void_p, c_void_p, c_size_t]),
@@ -273,6 +292,12 @@ def load(path: str | None = None):
                                           POINTER(_Err)]),
         "nzcb_debug_p256_mul2": (c_int, [c_void_p, ctypes.c_char_p, ctypes.c_char_p, c_size_t, u8p, POINTER(_Err)]),
         "nzcb_debug_p256_timings": (c_int, [POINTER(c_double), c_int]),
+        "nzcb_nzcp_pass_layout": (None, [POINTER(c_uint32)]),
+        "nzcb_nzcp_decode": (c_int, [c_int, ctypes.c_char_p, POINTER(c_uint32), c_int, POINTER(NzcpParams),
+                                     ctypes.c_char_p, POINTER(NzcpPass), u8p, u8p, c_size_t, POINTER(_Err)]),
+        "nzcb_nzcp_decode_dev": (c_int, [c_int, c_void_p, c_void_p, c_int, POINTER(NzcpParams), c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_size_t, c_void_p, POINTER(_Err)]),
+        "nzcb_debug_nzcp_decode_timings": (c_int, [POINTER(c_double), c_int]),
     }
     lib.missing_symbols = []
     for name, (res, args) in sigs.items():
@@ -283,6 +308,11 @@ def load(path: str | None = None):
             continue
         fn.restype = res
         fn.argtypes = args
+    if "nzcb_nzcp_pass_layout" not in lib.missing_symbols:
+        lay = (c_uint32 * 3)()
+        lib.nzcb_nzcp_pass_layout(lay)
+        if list(lay) != [ctypes.sizeof(NzcpPass), NzcpPass.sig.offset, NzcpPass.tbs_sha256.offset]:
+            raise OSError(f"NzcpPass does not mirror nzcb_nzcp_pass: the library reports {list(lay)}")
     _lib = lib
     return lib
 
@@ -351,6 +381,102 @@ def nzcp_witness_dev(dev_inputs: int, count: int, params: dict = NZCP_LIVE, devi
 def nzcp_records_from_bytes(raw: bytes, count: int) -> list:
     size = ctypes.sizeof(NzcpRecord)
     return [_record_dict(NzcpRecord.from_buffer_copy(raw[i * size:(i + 1) * size])) for i in range(count)]
+
+
+def _pass_dict(r: NzcpPass) -> dict:
+    """A record with its strings cut to their stored bytes: kid, cti, sig as bytes, iss as str. A
+    field the pass does not have (its `present` bit is clear) is None."""
+    has = lambda bit: bool(r.present & bit)  # noqa: E731
+    return {
+        "status": r.status, "status_name": PASS_STATUS_NAMES[r.status], "detail": r.detail, "version": r.version,
+        "present": r.present, "alg": r.alg if has(PASS_HAS_ALG) else None,
+        "kid": bytes(r.kid)[:min(r.kid_len, 32)] if has(PASS_HAS_KID) else None, "kid_len": r.kid_len,
+        "iss": bytes(r.iss)[:min(r.iss_len, 64)].decode(errors="replace") if has(PASS_HAS_ISS) else None,
+        "iss_len": r.iss_len, "nbf": r.nbf if has(PASS_HAS_NBF) else None,
+        "exp": r.exp if has(PASS_HAS_EXP) else None,
+        "cti": bytes(r.cti)[:min(r.cti_len, 32)] if has(PASS_HAS_CTI) else None, "cti_len": r.cti_len,
+        "sig": bytes(r.sig) if has(PASS_HAS_SIG) else None, "sig_len": r.sig_len, "cose_len": r.cose_len,
+        "protected_off": r.protected_off, "protected_len": r.protected_len, "payload_off": r.payload_off,
+        "payload_len": r.payload_len, "tbs_len": r.tbs_len, "fits": r.fits, "tbs_sha256": bytes(r.tbs_sha256),
+    }
+
+
+def nzcp_passes_from_bytes(raw: bytes, count: int) -> list:
+    size = ctypes.sizeof(NzcpPass)
+    return [_pass_dict(NzcpPass.from_buffer_copy(raw[i * size:(i + 1) * size])) for i in range(count)]
+
+
+def pack_uris(uris):
+    """URIs (str or bytes) -> (their bytes back to back, count + 1 offsets as a c_uint32 array)."""
+    raw = [u.encode("utf-8", "surrogateescape") if isinstance(u, str) else bytes(u) for u in uris]
+    offs, at = [0], 0
+    for b in raw:
+        at += len(b)
+        offs.append(at)
+    if at > 1 << 31:
+        raise ValueError("more than 2^31 bytes of URIs")
+    return b"".join(raw), (c_uint32 * len(offs))(*offs)
+
+
+def nzcp_decode_raw(uris, params: dict | None = None, data20=None, device: int = 0, want_tbs: int = 0,
+                    offsets=None):
+    """include/nzcb.h nzcb_nzcp_decode over host buffers -> (record bytes, input bytes or None,
+    ToBeSigned bytes at stride want_tbs or None). uris: a list, or the packed bytes with `offsets`
+    (count + 1 integers, passed on as they are). data20: count x 20 bytes, or None for zeros."""
+    lib = load()
+    if offsets is None:
+        blob, offs = pack_uris(uris)
+    else:
+        blob, offs = bytes(uris), (c_uint32 * len(offsets))(*offsets)
+    count = len(offs) - 1
+    if data20 is not None:
+        data20 = b"".join(data20) if isinstance(data20, (list, tuple)) else bytes(data20)
+        if len(data20) != 20 * count:
+            raise ValueError("data is 20 bytes per pass")
+    prm = NzcpParams(**params) if params else None
+    recs = (NzcpPass * max(count, 1))()
+    inputs = _out(lib.nzcb_nzcp_input_signals(ctypes.byref(prm)) * 32 * count) if prm else None
+    tbs = _out(want_tbs * count) if want_tbs else None
+    err = _Err()
+    _check(lib.nzcb_nzcp_decode(device, blob, offs, count, ctypes.byref(prm) if prm else None, data20, recs, inputs,
+                                tbs, want_tbs, ctypes.byref(err)), err)
+    size = ctypes.sizeof(NzcpPass)
+    return (bytes(recs)[:size * count],
+            bytes(inputs)[:lib.nzcb_nzcp_input_signals(ctypes.byref(prm)) * 32 * count] if prm else None,
+            bytes(tbs)[:want_tbs * count] if want_tbs else None)
+
+
+def nzcp_decode(uris, params: dict | None = None, data20=None, device: int = 0):
+    """Pass URIs -> one dict per pass (include/nzcb.h nzcb_nzcp_pass: status, status_name, detail,
+    version, alg, kid, iss, nbf, exp, cti, sig, the lengths and offsets, tbs_len, tbs_sha256, fits;
+    absent fields None), decoded on GPU `device` or on the host (NZCP_HOST). With `params`
+    (NZCP_LIVE, NZCP_EXAMPLE) returns (dicts, inputs): pass i's input signals for nzcp_witness /
+    WitnessProgram.run at inputs[i * nzcp_input_signals(params) * 32:], zeros where fits = 0."""
+    uris = list(uris)
+    recs, inputs, _ = nzcp_decode_raw(uris, params, data20, device)
+    out = nzcp_passes_from_bytes(recs, len(uris))
+    return (out, inputs) if params else out
+
+
+def nzcp_decode_dev(dev_uris: int, dev_offsets: int, count: int, dev_passes: int, params: dict | None = None,
+                    dev_data20: int | None = None, dev_inputs: int | None = None, dev_tbs: int | None = None,
+                    tbs_stride: int = 0, device: int = 0, stream: int | None = None):
+    """Device-pointer variant, asynchronous on `stream`; see nzcb_nzcp_decode_dev. dev_passes takes
+    count x sizeof(NzcpPass) bytes (nzcp_passes_from_bytes reads them once copied down); record i's
+    sig and tbs_sha256 are where P256Key.verify_dev reads them with stride sizeof(NzcpPass)."""
+    lib = load()
+    err = _Err()
+    prm = NzcpParams(**params) if params else None
+    _check(lib.nzcb_nzcp_decode_dev(device, dev_uris, dev_offsets, count, ctypes.byref(prm) if prm else None,
+                                    dev_data20, dev_passes, dev_inputs, dev_tbs, tbs_stride, stream,
+                                    ctypes.byref(err)), err)
+
+
+def nzcp_decode_timings() -> list:
+    """Milliseconds of this thread's last nzcp_decode: the kernel, the call."""
+    ms = (c_double * 2)()
+    n = load().nzcb_debug_nzcp_decode_timings(ms, 2)
+    return list(ms)[:n]
 
 
 class Engine:
@@ -1090,6 +1216,68 @@ class P256Key:
             d["valid"] = st == SIG_OK
             d["reason"] = None if st == SIG_OK else ("invalid signature" if st == SIG_INVALID
                                                       else "signature out of range")
+        return out
+
+    def verify_uris(self, uris) -> list:
+        """verify_passes with the decoding on the key's device too: the URIs' bytes go up, the
+        decode kernel (nzcp_decode_dev) and the verification, which reads each record's digest and
+        signature in place, run on one stream, and the records come down once. The dicts have
+        verify_passes' keys and reason texts, except that a pass that does not decode is reported
+        as "malformed pass: <status name> at <detail>" (PASS_STATUS_NAMES). The record keeps the
+        first 32 bytes of a kid and 64 of an iss. A host key decodes and verifies on the host."""
+        uris = list(uris)
+        n = len(uris)
+        if not n:
+            return []
+        size, off_h, off_s = ctypes.sizeof(NzcpPass), NzcpPass.tbs_sha256.offset, NzcpPass.sig.offset
+        if self.device == P256_HOST:
+            raw, _, _ = nzcp_decode_raw(uris, device=NZCP_HOST)
+            statuses = self.verify(raw[off_h:], raw[off_s:], hash_stride=size, sig_stride=size)
+        else:
+            blob, offs = pack_uris(uris)
+            lib = self.lib
+            prev, stream, bufs = c_int(-1), c_void_p(), []
+            if lib.hipGetDevice(ctypes.byref(prev)) or lib.hipSetDevice(self.device):
+                raise NzcbError(10, "cannot select the key's device")
+            try:
+                for nbytes in (len(blob), 4 * (n + 1), size * n):
+                    bufs.append(lib.nzcb_dev_alloc_on(self.device, max(nbytes, 4)))
+                    if not bufs[-1]:
+                        raise MemoryError("device allocation failed")
+                d_uris, d_off, d_rec = bufs
+                if blob:
+                    h2d(d_uris, blob)
+                h2d(d_off, bytes(offs))
+                if lib.hipStreamCreate(ctypes.byref(stream)):
+                    raise NzcbError(10, "cannot create a HIP stream")
+                nzcp_decode_dev(d_uris, d_off, n, d_rec, device=self.device, stream=stream)
+                statuses = self.verify_dev(d_rec + off_h, size, d_rec + off_s, size, n, stream)
+                raw = d2h(d_rec, size * n)
+            finally:
+                if stream:
+                    lib.hipStreamDestroy(stream)
+                for p in bufs:
+                    if p:
+                        lib.nzcb_dev_free(p)
+                lib.hipSetDevice(prev)
+        out = []
+        for r, st in zip(nzcp_passes_from_bytes(raw, n), statuses):
+            d = {"valid": False, "status": None, "reason": None, "alg": None, "kid": None, "iss": None,
+                 "nbf": None, "exp": None}
+            out.append(d)
+            if r["status"]:
+                d["reason"] = f"malformed pass: {r['status_name']} at {r['detail']}"
+                continue
+            d.update(alg=r["alg"], kid=r["kid"], iss=r["iss"], nbf=r["nbf"], exp=r["exp"])
+            if d["alg"] != -7:
+                d["reason"] = f"unsupported alg {d['alg']} (ES256 is -7)"
+            elif r["sig"] is None or r["sig_len"] != 64:
+                d["reason"] = "signature is not 64 bytes"
+            else:   # every other pass's verdict, computed over a zeroed signature, is dropped
+                d["status"] = st
+                d["valid"] = st == SIG_OK
+                d["reason"] = None if st == SIG_OK else ("invalid signature" if st == SIG_INVALID
+                                                          else "signature out of range")
         return out
 
     def mul2(self, u1, u2) -> list:
