@@ -51,7 +51,8 @@ int nzcb_debug_inject_fault(nzcb_ctx* ctx, int kind);
  * over `count` host items of 32-bit limb words (9 per value), for tests against exact
  * integers. op 1: mul_shoup(x, w, ws) (27 words in, 9 out); 2: mul_shoup_x2 (54 / 18);
  * 3: mul29<Fq29>(a, b) (18 / 9); 4: mul29x2<Fr29>(a, b, c, d) (36 / 18); 5: sqr29x2(a, c)
- * (18 / 18); 6: mul2sum29(a, b, c, d) (36 / 9). Synchronous; count <= 2^24. */
+ * (18 / 18); 6: mul2sum29(a, b, c, d) (36 / 9); 7: div2k29(x, K) (10 words in: x, then K in
+ * 1..28; 9 out). Synchronous; count <= 2^24. */
 int nzcb_debug_f29(int device, int op, const uint32_t* in, size_t count, uint32_t* out, nzcb_err* err);
 
 /* ---- Synthetic circuit + setup ------- */
@@ -78,6 +79,13 @@ int nzcb_engine_ntt(nzcb_engine* e, const uint8_t* in_lem, uint8_t* out_lem, int
  * out: 64-byte affine x||y LE normal (infinity = zeros). */
 int nzcb_engine_msm(nzcb_engine* e, const uint8_t* bases_lem, const uint8_t* scalars, size_t n, int scalars_mont,
                     uint8_t* out_affine, nzcb_err* err);
+/* The forward transform on the coset c<w> through a per-coset twiddle table (csrc/ntt.h
+ * ntt_coset_twiddles, NttIo::tw; the prover's round-3 inputs): builds the table for c (32-byte
+ * LEM) at 2^log_n and runs one transform, out[i] = sum_j in[j] (c w^i)^j over the
+ * n + fold_len input coefficients (fold_len <= n: those past n are folded in with x^n = c^n,
+ * as the prover folds the blinding terms). 1 <= log_n <= the engine's max_log_ntt. */
+int nzcb_debug_ntt_coset(nzcb_engine* e, const uint8_t* in_lem, uint8_t* out_lem, int log_n, const uint8_t* c_lem,
+                         int fold_len, nzcb_err* err);
 /* Device-resident variants for benchmarks (pointers from nzcb_dev_alloc, nzcb.h). */
 int nzcb_engine_ntt_dev(nzcb_engine* e, const void* in, void* out, int log_n, int inverse, nzcb_err* err);
 int nzcb_engine_msm_dev(nzcb_engine* e, const void* bases, const void* scalars, size_t n, int scalars_mont,

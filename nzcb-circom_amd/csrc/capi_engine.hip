@@ -227,6 +227,37 @@ int nzcb_engine_ntt(nzcb_engine* e, const uint8_t* in_lem, uint8_t* out_lem, int
   NZ_GUARD_END(err)
 }
 
+int nzcb_debug_ntt_coset(nzcb_engine* e, const uint8_t* in_lem, uint8_t* out_lem, int log_n, const uint8_t* c_lem,
+                         int fold_len, nzcb_err* err) {
+  NZ_GUARD_BEGIN
+  Engine& g = e->eng;
+  if (log_n < 1 || log_n > g.ntt_tables.max_log || fold_len < 0 || (size_t)fold_len > (size_t(1) << log_n))
+    throw Error(NZCB_ERR_ARG, "ntt coset: 1 <= log_n <= the engine's, 0 <= fold_len <= n");
+  NZ_HIP(hipSetDevice(g.device));
+  const size_t n = size_t(1) << log_n;
+  Fr c;
+  std::memcpy(c.v, c_lem, 32);
+  DevBuf<Fr> a(n + (size_t)fold_len), b(n);
+  DevBuf<NttTables::Tw> tw(n - 1);
+  NZ_HIP(hipMemcpyAsync(a.p, in_lem, (n + (size_t)fold_len) * 32, hipMemcpyHostToDevice, g.stream));
+  ntt_coset_twiddles(g.ntt_tables, c, log_n, tw.p, g.stream);
+  NttIo io;
+  io.in_len = n;
+  io.tw = tw.p;
+  if (fold_len) {  // x^n = c^n on the coset
+    Fr d = pow_u64(c, (uint64_t)n);
+    for (int k = 0; k < 5; k++) d = d + d;  // Montgomery-261 operand
+    io.fold_len = (size_t)fold_len;
+    io.fold_n = n;
+    io.fold_f = split29(d);
+  }
+  ntt(g.ntt_tables, a.p, b.p, log_n, false, g.stream, nullptr, &io);
+  NZ_HIP(hipMemcpyAsync(out_lem, b.p, n * 32, hipMemcpyDeviceToHost, g.stream));
+  NZ_HIP(hipStreamSynchronize(g.stream));
+  return 0;
+  NZ_GUARD_END(err)
+}
+
 int nzcb_engine_time_ntt(nzcb_engine* e, const void* in, void* out, int log_n, int inverse, int reps, double* ms,
                          nzcb_err* err) {
   NZ_GUARD_BEGIN

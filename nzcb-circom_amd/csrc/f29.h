@@ -669,6 +669,34 @@ NZ_HD Fr from_mont_fr29(const Fr& a) {
   return join_fr29(r);
 }
 
+// x 2^-K mod r for 1 <= K <= 28 and a normalized x (the inverse NTT's 1/N = 2^-L): one word
+// step of a Montgomery reduction. m = x_0 (-r^-1) mod 2^K makes t = x + m r a multiple of
+// 2^K (9 mads into 29-bit columns, each below 2^29 + 2^57 + a carry < 2^29), and t / 2^K is
+// a shift across the limbs: the result is congruent to x 2^-K, normalized, and
+// below x / 2^K + r since m < 2^K. t itself has up to K bits more than x: its top column
+// (bits 232 and up, < 2^22 2^K + x_8) stays in the 64-bit accumulator until the shift.
+NZ_HD F29 div2k29(const F29& x, int K) {
+  using Q = Fr29;
+  const uint32_t m = (x.v[0] * Q::INV) & ((1u << K) - 1u);
+  uint32_t t[8];
+  uint64_t acc = 0;
+#pragma unroll
+  for (int l = 0; l < 8; l++) {
+    acc += x.v[l];
+    mad29c(acc, m, Q::P[l]);
+    t[l] = (uint32_t)acc & Q::MASK;
+    acc >>= 29;
+  }
+  acc += x.v[8];
+  mad29c(acc, m, Q::P[8]);
+  F29 r;
+#pragma unroll
+  for (int l = 0; l < 7; l++) r.v[l] = (t[l] >> K) | ((t[l + 1] << (29 - K)) & Q::MASK);
+  r.v[7] = (t[7] >> K) | ((uint32_t)(acc << (29 - K)) & Q::MASK);
+  r.v[8] = (uint32_t)(acc >> K);
+  return r;
+}
+
 // Montgomery-256 Fr -> the same value at exponent 261 (x 2^5 < 32 r, normalized): the
 // 261-bit shift of the limbs, no product (x < 2^254, so the top limb stays < 2^27)
 NZ_HD F29 fr_to261(const Fr& x) {

@@ -10,8 +10,8 @@ namespace nzcb {
 namespace {
 
 // words in / out per item, by op
-constexpr int kIn[7] = {0, 27, 54, 18, 36, 18, 36};
-constexpr int kOut[7] = {0, 9, 18, 9, 18, 18, 9};
+constexpr int kIn[8] = {0, 27, 54, 18, 36, 18, 36, 10};
+constexpr int kOut[8] = {0, 9, 18, 9, 18, 18, 9, 9};
 
 __device__ __forceinline__ F29 ld(const uint32_t* p) {
   F29 r;
@@ -50,8 +50,11 @@ __global__ void __launch_bounds__(64) k_f29_check(const uint32_t* __restrict__ i
     sqr29x2(ld(a), ld(a + 9), r1, r2);
     st(o, r1);
     st(o + 9, r2);
-  } else {  // (a b + c d) 2^-261 mod q
+  } else if constexpr (OP == 6) {  // (a b + c d) 2^-261 mod q
     st(o, mul2sum29(ld(a), ld(a + 9), ld(a + 18), ld(a + 27)));
+  } else {  // x 2^-K mod r: (x, K), K in 1..28 (a K outside is clamped, never a wild shift)
+    const uint32_t k = a[9];
+    st(o, div2k29(ld(a), (int)(k < 1 ? 1 : k > 28 ? 28 : k)));
   }
 }
 
@@ -73,8 +76,8 @@ extern "C" int nzcb_debug_f29(int device, int op, const uint32_t* in, size_t cou
     }
     return code;
   };
-  if (op < 1 || op > 6 || (count && (!in || !out)) || count > (size_t(1) << 24))
-    return fail(NZCB_ERR_ARG, "f29 check: op 1..6, count <= 2^24");
+  if (op < 1 || op > 7 || (count && (!in || !out)) || count > (size_t(1) << 24))
+    return fail(NZCB_ERR_ARG, "f29 check: op 1..7, count <= 2^24");
   try {
     if (count) {
       NZ_HIP(hipSetDevice(device));
@@ -86,7 +89,8 @@ extern "C" int nzcb_debug_f29(int device, int op, const uint32_t* in, size_t cou
         case 3: launch<3>(din.p, dout.p, count); break;
         case 4: launch<4>(din.p, dout.p, count); break;
         case 5: launch<5>(din.p, dout.p, count); break;
-        default: launch<6>(din.p, dout.p, count); break;
+        case 6: launch<6>(din.p, dout.p, count); break;
+        default: launch<7>(din.p, dout.p, count); break;
       }
       NZ_HIP(hipGetLastError());
       NZ_HIP(hipMemcpy(out, dout.p, count * kOut[op] * 4, hipMemcpyDeviceToHost));

@@ -36,6 +36,9 @@ struct NttTables {
 //             1/N (the first pass then skips it).
 //   fold (a polynomial of degree < n + fold_len evaluated where x^n = d): input j <
 //             fold_len also adds in[j + fold_n] * d, before in_f (fold_f: d's operand)
+//   tw (forward only): the twiddles of a coset c<w> (ntt_coset_twiddles) instead of the
+//             tables' own: out[i] = sum_j in[j] (c w^i)^j with no product on the input; the
+//             transform's stage 0 then has the twiddle c^(N/2) where the plain one has 1
 struct NttIo {
   size_t in_len = ~size_t(0);
   const F29* in_f = nullptr;
@@ -45,7 +48,15 @@ struct NttIo {
   bool out_f_has_scale = false;
   size_t out_limit = ~size_t(0);
   uint32_t* out_flags = nullptr;
+  const NttTables::Tw* tw = nullptr;
 };
+
+// The forward twiddles of size 2^log_n (<= t.max_log) for the coset c<w>, 2^log_n - 1 entries
+// in the layout of NttTables::fwd29: entry 2^g - 1 + k is c^(2^(log_n-1-g)) w_(2^(g+1))^k.
+// In a decimation-in-time transform A(c w^i) = E(c^2 w^2i) + c w^i O(c^2 w^2i): the coset
+// factor c^j of coefficient j is the same recursion with these twiddles. Unlike the plain
+// table (whose prefix serves every smaller size) a coset table is for its own log_n only.
+void ntt_coset_twiddles(const NttTables& t, const Fr& c, int log_n, NttTables::Tw* out, hipStream_t st);
 
 // out = NTT(in) (inverse: out = (1/N) * iNTT(in)), N = 2^log_n <= 2^max_log.
 // Natural order in and out; in != out required (first pass gathers in bit-reversed order).

@@ -60,17 +60,52 @@ ntt_stage_table_kernel(Fr* __restrict__ out, const Fr* __restrict__ full, int L,
 // the Shoup operand pair of a twiddle given in Montgomery-256 form (s = w 2^256 mod r):
 // w = from_mont(s), and ws = floor(w 2^261 / r) from m = w 2^261 mod r (= s 2^5 mod r):
 // w 2^261 = ws r + m, so ws = -m r^-1 mod 2^261 (exact; ws < 2^261), a low-half product
+__device__ __forceinline__ NttTables::Tw tw29_of(const Fr& s) {
+  Fr m = s;
+#pragma unroll
+  for (int k = 0; k < 5; k++) m = m + m;
+  NttTables::Tw t;
+  t.w = split29(from_mont(s));
+  t.ws = mul_lo261(split29(m), f29_const(Fr29::NINV));
+  return t;
+}
 __global__ void __launch_bounds__(256) ntt_tw29_kernel(NttTables::Tw* __restrict__ out, const Fr* __restrict__ tw,
                                                        size_t count) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= count) return;
-  Fr m = tw[i];
-#pragma unroll
-  for (int k = 0; k < 5; k++) m = m + m;
-  NttTables::Tw t;
-  t.w = split29(from_mont(tw[i]));
-  t.ws = mul_lo261(split29(m), f29_const(Fr29::NINV));
-  out[i] = t;
+  out[i] = tw29_of(tw[i]);
+}
+
+// A coset's twiddles (ntt.h ntt_coset_twiddles) from the plain stage table: entry
+// 2^g - 1 + k is the plain twiddle w (canonical) times stage g's factor f_g = c^(2^(L-1-g)),
+// given as split29 of f_g 2^517 mod r: the product is (w f_g) 2^256, below 2r, normalized,
+// the Montgomery-256 form tw29_of takes.
+struct CosetStageF {
+  F29 f[28];
+};
+__global__ void __launch_bounds__(256)
+ntt_coset_tw29_kernel(NttTables::Tw* __restrict__ out, const NttTables::Tw* __restrict__ plain, CosetStageF cf,
+                      size_t count) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  const int g = 63 - __clzll((unsigned long long)(i + 1));  // i + 1 in [2^g, 2^(g+1))
+  out[i] = tw29_of(join_fr29(mul29<Fr29>(plain[i].w, cf.f[g])));
+}
+
+void ntt_coset_twiddles(const NttTables& t, const Fr& c, int L, NttTables::Tw* out, hipStream_t st) {
+  if (L < 1 || L > t.max_log || L > 28) throw Error(NZCB_ERR_ARG, "ntt coset twiddles: size exceeds table");
+  CosetStageF cf = {};
+  Fr f = c;  // c^(2^(L-1-g)), from the last stage down
+  for (int g = L - 1; g >= 0; g--) {
+    Fr op = to_mont(f);  // f 2^512
+    for (int k = 0; k < 5; k++) op = op + op;
+    cf.f[g] = split29(op);
+    f = sqr(f);
+  }
+  const size_t total = (size_t(1) << L) - 1;
+  hipLaunchKernelGGL(ntt_coset_tw29_kernel, dim3(grid_for(total, 256, 1u << 30)), dim3(256), 0, st, out,
+                     (const NttTables::Tw*)t.fwd29.p, cf, total);
+  NZ_HIP(hipGetLastError());
 }
 
 void NttTables::init(int L, hipStream_t st) {
@@ -119,7 +154,17 @@ void NttTables::init(int L, hipStream_t st) {
 //    included, >= t's) adds at most 4r to the value bound of its inputs, so after the L <= 24
 //    stages of a transform from inputs < 2.4 r the values are < 99 r < 2^260.3 (every
 //    product input < 2^261 holds throughout, no value reduction is ever needed);
-//  * limbs: a radix-4 group's outputs are < 2^31.3 before normalisation, its products'
+//  * stages (0, 1) of a plain transform: stage 1's first twiddle is w_4^0 = 1, so u2 = y2 =
+//    x2 + x3 stays unreduced (limbs < 2^30) and z2 = y0 + 8r - y2 borrows 2 K4 (sub8r_nn29):
+//    z2 < 4.8 r + 8 r = 12.8 r where two butterflies give at most 2.4 r + 8 r, so the
+//    transform's values are < 101.4 r, still < 2^260.3 = 104 r; z2's limbs are
+//    < 2^30 + 2 K4_l < 2^31.6, z0's < 2^31, both inside norm29's 32-bit limbs;
+//  * a coset transform (NttIo::tw) has the twiddle c^(N/2) at stage 0 where the plain one
+//    has 1: one more product, the same + 4r per stage; its fold prologue's sum is < 2.4 r
+//    with limbs < 2^30, inside mul_shoup's input bound (< 2^261, limbs < 2^30.6) already, and
+//    is made canonical as in every fold without in_f (at most 6 elements per transform);
+//  * limbs: a radix-4 group's outputs are < 2^31.3 before normalisation (< 2^31.6 in the
+//    unit-twiddle case above), its products'
 //    inputs < 2^30.7; the outputs are normalized (norm29) once per group (and after the
 //    odd radix-2 stage), so every group starts from limbs < 2^29;
 //  * the last pass maps v < 128 r to canonical Fr: q = floor(v_8 / (r_8 + 1)) <= v / r
@@ -172,6 +217,52 @@ __device__ __forceinline__ F29 sub4r_nn29(const F29& a, const F29& b) {  // a + 
   for (int l = 0; l < 9; l++) r.v[l] = a.v[l] + Fr29::K4[l] - b.v[l];
   return r;
 }
+// a + 8r - b for b the unnormalized sum of two normalized values < 3r each: every limb of
+// 2 K4, the top one included, is >= b's
+__device__ __forceinline__ F29 sub8r_nn29(const F29& a, const F29& b) {
+  F29 r;
+#pragma unroll
+  for (int l = 0; l < 9; l++) r.v[l] = a.v[l] + 2u * Fr29::K4[l] - b.v[l];
+  return r;
+}
+
+// One radix-4 group (two stages) on the tile elements i0..i3: wa the first stage's twiddle,
+// wb, wc the second stage's. UNIT: wa = wb = 1 (stages (0, 1) of a plain transform, wc = w_4):
+// t1, t3 and u2 = y2 = x2 + x3 stay as they are, and z2 = y0 + 8r - y2 (see the bounds above).
+template <bool UNIT>
+__device__ __forceinline__ void radix4_group(uint32_t* sl, int i0, int i1, int i2, int i3,
+                                             const NttTables::Tw* __restrict__ wa, const NttTables::Tw* __restrict__ wb,
+                                             const NttTables::Tw* __restrict__ wc) {
+  F29 t1 = tile_ld(sl, i1), t3 = tile_ld(sl, i3);
+  if (!UNIT) {
+    const NttTables::Tw w = *wa;
+    F29 p1, p3;
+    tw_mul2(t1, w, t3, w, p1, p3);
+    t1 = p1;
+    t3 = p3;
+  }
+  const F29 x0 = tile_ld(sl, i0), x2 = tile_ld(sl, i2);
+  const F29 y0 = add_nn29(x0, t1), y1 = sub4r_nn29(x0, t1);
+  const F29 y2 = add_nn29(x2, t3), y3 = sub4r_nn29(x2, t3);
+  F29 u2, u3, z2;
+  if (!UNIT) {
+    tw_mul2(y2, *wb, y3, *wc, u2, u3);
+    z2 = sub4r_nn29(y0, u2);
+  } else {
+    u2 = y2;
+    u3 = tw_mul(y3, *wc);
+    z2 = sub8r_nn29(y0, y2);
+  }
+  F29 z0 = add_nn29(y0, u2), z1 = add_nn29(y1, u3), z3 = sub4r_nn29(y1, u3);
+  norm29(z0);
+  norm29(z1);
+  norm29(z2);
+  norm29(z3);
+  tile_st(sl, i0, z0);
+  tile_st(sl, i1, z1);
+  tile_st(sl, i2, z2);
+  tile_st(sl, i3, z3);
+}
 
 // One pass of stages [s, s+q) on tiles of (2^q rows) x (2^logC columns). IN29: values from
 // the F29 scratch (else the Fr input, first pass only); OUT29: values to the F29 scratch
@@ -208,7 +299,8 @@ ntt29_pass_kernel(const Fr* in, const F29* in29, Fr* out, F29* out29, const NttT
           }
         }
         if (io.in_f) x = mul29<Fr29>(x, io.in_f[src]);
-        if (do_scale) x = mul29<Fr29>(x, scale29);
+        if (do_scale == 2) x = div2k29(x, L);  // 1/N = 2^-L
+        else if (do_scale) x = mul29<Fr29>(x, scale29);
       }
       tile_st(sl, e, x);
     }
@@ -224,7 +316,10 @@ ntt29_pass_kernel(const Fr* in, const F29* in29, Fr* out, F29* out29, const NttT
   }
   __syncthreads();
   const int nbf = n_el >> 1;
+  const int ngroups = n_el >> 2;
   const bool first = !IN29;
+  // a coset's twiddles: stage 0's is c^(N/2), not 1 (uniform; later passes have no stage 0)
+  const bool twist = !IN29 && io.tw != nullptr;
   int st = 0;
   if (sparse4 && blockIdx.x != 0) {
     // zero-padded input past tile 0: of every four bit-reversed rows 4m..4m+3 only row 4m
@@ -249,7 +344,7 @@ ntt29_pass_kernel(const Fr* in, const F29* in29, Fr* out, F29* out29, const NttT
       const size_t k = first ? 0 : (lo0 + c);
       const F29 x0 = tile_ld(sl, i0);
       const F29 x1 = tile_ld(sl, i1);
-      const F29 tt = g ? tw_mul(x1, twg[k]) : x1;
+      const F29 tt = (g || twist) ? tw_mul(x1, twg[k]) : x1;
       F29 y0 = add_nn29(x0, tt), y1 = sub4r_nn29(x0, tt);
       norm29(y0);
       norm29(y1);
@@ -258,12 +353,22 @@ ntt29_pass_kernel(const Fr* in, const F29* in29, Fr* out, F29* out29, const NttT
     }
     __syncthreads();
     st = 1;
+  } else if (!IN29 && !twist && q >= 2) {
+    // stages (0, 1) of a plain transform: the twiddles are 1, 1 and (1, w_4)
+    const int b = tid;
+    if (b < ngroups) {
+      const int c = b & (C - 1);
+      const int j = (b >> logC) << 2;
+      radix4_group<true>(sl, (j << logC) + c, ((j + 1) << logC) + c, ((j + 2) << logC) + c, ((j + 3) << logC) + c,
+                         tw, tw, tw + 2);
+    }
+    __syncthreads();
+    st = 2;
   }
-  const int ngroups = n_el >> 2;
 #pragma unroll 1
   for (; st < q; st += 2) {
     const int h = 1 << st;
-    const int g = s + st;
+    const int g = s + st;  // > 0, or 0 with a coset's twiddles: every twiddle is a real factor
     const NttTables::Tw* __restrict__ twa = tw + (((size_t)1 << g) - 1);
     const NttTables::Tw* __restrict__ twb = tw + (((size_t)1 << (g + 1)) - 1);
     const int b = tid;
@@ -274,31 +379,8 @@ ntt29_pass_kernel(const Fr* in, const F29* in29, Fr* out, F29* out29, const NttT
       const int j = ((pr >> st) << (st + 2)) | low;
       const size_t ka = first ? (size_t)low : (((size_t)low << s) + lo0 + c);
       const size_t kc = first ? (size_t)(low + h) : (((size_t)(low + h) << s) + lo0 + c);
-      const int i0 = (j << logC) + c, i1 = ((j + h) << logC) + c, i2 = ((j + 2 * h) << logC) + c,
-                i3 = ((j + 3 * h) << logC) + c;
-      F29 t1 = tile_ld(sl, i1), t3 = tile_ld(sl, i3);
-      if (g) {
-        const NttTables::Tw wa = twa[ka];
-        F29 p1, p3;
-        tw_mul2(t1, wa, t3, wa, p1, p3);
-        t1 = p1;
-        t3 = p3;
-      }
-      const F29 x0 = tile_ld(sl, i0), x2 = tile_ld(sl, i2);
-      const F29 y0 = add_nn29(x0, t1), y1 = sub4r_nn29(x0, t1);
-      const F29 y2 = add_nn29(x2, t3), y3 = sub4r_nn29(x2, t3);
-      F29 u2, u3;
-      const NttTables::Tw wb = twb[ka], wc = twb[kc];
-      tw_mul2(y2, wb, y3, wc, u2, u3);
-      F29 z0 = add_nn29(y0, u2), z2 = sub4r_nn29(y0, u2), z1 = add_nn29(y1, u3), z3 = sub4r_nn29(y1, u3);
-      norm29(z0);
-      norm29(z1);
-      norm29(z2);
-      norm29(z3);
-      tile_st(sl, i0, z0);
-      tile_st(sl, i1, z1);
-      tile_st(sl, i2, z2);
-      tile_st(sl, i3, z3);
+      radix4_group<false>(sl, (j << logC) + c, ((j + h) << logC) + c, ((j + 2 * h) << logC) + c,
+                          ((j + 3 * h) << logC) + c, twa + ka, twb + ka, twb + kc);
     }
     __syncthreads();
   }
@@ -372,13 +454,18 @@ void ntt(const NttTables& t, const Fr* in, Fr* out, int L, bool inverse_dir, hip
   if (in == out) throw Error(NZCB_ERR_ARG, "ntt requires in != out");
   F29* scr = (F29*)(scratch29 ? scratch29 : t.scratch29.p);
   if (L > 8 && !scratch29 && t.scratch29.n < ((size_t)9 << L)) throw Error(NZCB_ERR_INTERNAL, "ntt: no scratch");
-  const NttTables::Tw* tw = inverse_dir ? t.inv29.p : t.fwd29.p;
+  if (io.tw && inverse_dir) throw Error(NZCB_ERR_ARG, "ntt: coset twiddles are for the forward transform");
+  const NttTables::Tw* tw = io.tw ? io.tw : inverse_dir ? t.inv29.p : t.fwd29.p;
   Fr sc = Fr::one();
-  int do_scale = 0;
+  int do_scale = 0;  // 1: a product by scale29; 2: exactly 1/N = 2^-L, a shift (f29.h div2k29)
   if (inverse_dir && !io.out_f_has_scale) {
-    Fr two = Fr::one() + Fr::one();
-    sc = inverse(pow_u64(two, (uint64_t)L));  // N^-1
-    do_scale = 1;
+    if (!scale && L >= 1 && L <= 28) {
+      do_scale = 2;
+    } else {
+      Fr two = Fr::one() + Fr::one();
+      sc = inverse(pow_u64(two, (uint64_t)L));  // N^-1
+      do_scale = 1;
+    }
   }
   if (scale) {
     sc = do_scale ? sc * *scale : *scale;

@@ -82,7 +82,8 @@ struct Prover {
   // coefficients of A, B, C, Z and sigma (prove(), round 3)
   bool quot3 = false;
   DevBuf<Fr> cq3, cs3, cl3;       // Qm..Qc (5 x 3n), sigma1..3 (3 x 3n), L_j (nl x 3n)
-  DevBuf<F29> tw3, itw3;          // c_j^k and c_j^-k / 4n (3 x n each), mul_fr29 operands
+  DevBuf<NttTables::Tw> ctw3;     // the forward twiddles of c_j H (3 x (n - 1), ntt_coset_twiddles)
+  DevBuf<F29> itw3;               // c_j^-k / (4n Z_H(c_j)) (3 x n), mul_fr29 operands
   Fr d3[3];                       // c_j^n = g^n w4^(j n)
   Fr sig_top[3][4];               // sigma_k coefficients n-4 .. n-1
   // per-proof working set
@@ -91,6 +92,7 @@ struct Prover {
   DevBuf<Fr> A, B, C, Z;          // n (A, B, C: n + 2, the blinding scalars b_lo, b_hi at n, n + 1)
   DevBuf<Fr> pol_a, pol_b, pol_c, pol_z;  // n+2 / n+3
   DevBuf<Fr> A4, B4, C4, Z4, T, Tz, t;  // 4n (A4..Z4: coset evaluations)
+  DevBuf<Fr> bx_lo;               // 4096: beta x_lo[i] (the three-coset quotient's beta x)
   DevBuf<Fr> pol_r, pol_wxi, pol_wxiw;    // n+3, n+6, n+3
   DevBuf<Fr> blind;               // 12 (index 0 unused)
   DevBuf<Fr> scan_tmp;            // tile totals / heads of the round-2 and round-5 scans, and their levels

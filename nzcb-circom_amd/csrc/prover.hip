@@ -691,14 +691,19 @@ __device__ __forceinline__ F29 q29_pi(const Fr* __restrict__ cl, const Fr* __res
 // i = j n + m (x = g w4^(4m + j), Z(w x) at j n + (m + 1) mod n, 1/Z_H by j); otherwise
 // the 4n coset g<w4> in natural order (x_i = g w4^i, Z(w x) at i + 4, 1/Z_H by i mod 4).
 // Every array holds npts = 3n or 4n points per polynomial.
-// 4 waves per SIMD (128 VGPRs, 24 B scratch) instead of the compiler's 3 (130 VGPRs):
+// THREE leaves two per-point products to tables: 1 / Z_H(c_j) is part of the inverse
+// transform's per-coset output factors (itw3; the transform is linear and nothing reads T in
+// between), so T holds the numerator N(x) itself, and with k1 = 2, k2 = 3 beta x comes as
+// (beta xlo[i]) xhi[j] from the per-proof table bxlo (k_beta_xlo), x itself is not formed.
+// 4 waves per SIMD (128 VGPRs, 16 B scratch) instead of the compiler's 3 (130 VGPRs):
 // 1.084 -> 1.011 ms isolated, bench unchanged (profiles/r4_env_q4_ab.txt)
 template <bool THREE>
 __global__ void __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(4, 8)))
 k_quotient_coset29(const Fr* __restrict__ A, const Fr* __restrict__ B, const Fr* __restrict__ C,
                    const Fr* __restrict__ Z, const Fr* __restrict__ cq, const Fr* __restrict__ cs,
                    const Fr* __restrict__ cl, uint32_t npub, const Fr* __restrict__ Apub, size_t n,
-                   const Fr* __restrict__ xlo, const Fr* __restrict__ xhi, QArgs29 q, Fr* __restrict__ T) {
+                   const Fr* __restrict__ xlo, const Fr* __restrict__ xhi, const Fr* __restrict__ bxlo, QArgs29 q,
+                   Fr* __restrict__ T) {
   const size_t n4 = (THREE ? 3 : 4) * n;  // points per array
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n4) return;
@@ -715,7 +720,7 @@ k_quotient_coset29(const Fr* __restrict__ A, const Fr* __restrict__ B, const Fr*
     izw = (i + 4) & (n4 - 1);
     cj = (int)(i & 3);
   }
-  const F29 a = split29(A[i]), b = split29(B[i]), c = split29(C[i]), z = split29(Z[i]);
+  const F29 a = split29(A[i]), b = split29(B[i]), c = split29(C[i]);
   // gate: qm a b + ql a + qr b + qo c + qc - sum_j L_j Apub_j
   F29 gate;
   {
@@ -726,9 +731,11 @@ k_quotient_coset29(const Fr* __restrict__ A, const Fr* __restrict__ B, const Fr*
   if (npub > 0) gate = add29(gate, q29_pi(cl, Apub, 0, npub < 4 ? npub : 4, n4, i));
   if (npub > 4) gate = add29(gate, q29_pi(cl, Apub, 4, npub - 4, n4, i));  // < 7r
   // permutation: (a + b x + g)(b + b k1 x + g)(c + b k2 x + g) z - (a + b s1 + g)(..)(..) z(w x)
-  const F29 x = mul29<Fr29>(split29(xlo[ix & 4095]), split29(xhi[ix >> 12]));
-  const F29 bx = mul29<Fr29>(q.beta, x);                   // < 2r
-  const F29 bx2 = q.k23 ? add29(bx, bx) : mul29<Fr29>(q.bk1, x);  // < 4r
+  const F29 z = split29(Z[i]);  // loaded after the gate: 16 B of scratch (4n form: none) against 44 / 48
+  const bool bxt = THREE && q.k23;  // beta x straight from the table product (x below is then beta x)
+  const F29 x = mul29<Fr29>(split29((bxt ? bxlo : xlo)[ix & 4095]), split29(xhi[ix >> 12]));
+  const F29 bx = bxt ? x : mul29<Fr29>(q.beta, x);                 // < 2r
+  const F29 bx2 = q.k23 ? add29(bx, bx) : mul29<Fr29>(q.bk1, x);   // < 4r
   const F29 bx3 = q.k23 ? add29(bx2, bx) : mul29<Fr29>(q.bk2, x);  // < 6r
   const F29 f1 = add29(add29(a, bx), q.gamma);   // < 4r
   const F29 f2 = add29(add29(b, bx2), q.gamma);  // < 6r
@@ -742,7 +749,15 @@ k_quotient_coset29(const Fr* __restrict__ A, const Fr* __restrict__ B, const Fr*
   const F29 pa[2] = {q.alpha, q.alpha2};
   const F29 pb[2] = {sub29(num, den, Fr29::K2), mul29<Fr29>(add29(z, q.negone), split29(cl[i]))};
   const F29 S = add29(gate, mulsum29<Fr29, 2>(pa, pb));  // < 9r
-  T[i] = join_fr29(mul29<Fr29>(S, q.zhinv[cj]));
+  T[i] = THREE ? canon_fr29(S) : join_fr29(mul29<Fr29>(S, q.zhinv[cj]));
+}
+
+// bxlo[i] = beta xlo[i] (xlo: g w4^i 2^5, the quotient's low coset table; beta at exponent
+// 261), canonical, once per proof: the three-coset quotient's beta x by one product
+__global__ void __launch_bounds__(kT)
+k_beta_xlo(const Fr* __restrict__ xlo, F29 beta, size_t count, Fr* __restrict__ bxlo) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < count) bxlo[i] = join_fr29(mul29<Fr29>(beta, split29(xlo[i])));
 }
 
 // The three-coset quotient's divisibility check: N vanishes on H iff every gate holds
@@ -1275,26 +1290,23 @@ Prover::Prover(const uint8_t* zkey_bytes, size_t len, int device) {
                          q_h.p + (size_t)k * n);
     NZ_HIP(hipGetLastError());
   }
-  if (quot3) {  // three-coset quotient: per-coset twists c_j^k and untwists c_j^-k / 4n, j < 3
+  if (quot3) {  // three-coset quotient: per-coset forward twiddles (the twist c_j^k is in the
+                // transform, ntt.h ntt_coset_twiddles) and untwists c_j^-k / (4n Z_H(c_j)), j < 3
     const size_t nhi3 = (n + 4095) / 4096;
-    tw3.alloc((size_t)3 * n);
+    ctw3.alloc((size_t)3 * (n - 1));
     itw3.alloc((size_t)3 * n);
     const Fr inv4n = inverse(fr_small(n4));
     DevBuf<Fr> lo, hi;
     for (int j = 0; j < 3; j++) {
       const Fr cj = g * pow_u64(w4, (uint64_t)j), cji = inverse(cj);
       d3[j] = pow_u64(cj, n);
-      table(lo, nlo, cj, one);
-      table(hi, nhi3, pow_u64(cj, 4096), one);
-      hipLaunchKernelGGL(k_factor29_table, dim3(grid_for(n, kT, 1u << 30)), dim3(kT), 0, s, tw3.p + (size_t)j * n,
-                         lo.p, hi.p, one, (size_t)n);
-      NZ_HIP(hipStreamSynchronize(s));  // lo / hi are reallocated below
+      ntt_coset_twiddles(eng->ntt_tables, cj, power, ctw3.p + (size_t)j * (n - 1), s);
       table(lo, nlo, cji, one);
       table(hi, nhi3, pow_u64(cji, 4096), one);
       hipLaunchKernelGGL(k_factor29_table, dim3(grid_for(n, kT, 1u << 30)), dim3(kT), 0, s, itw3.p + (size_t)j * n,
-                         lo.p, hi.p, inv4n, (size_t)n);
+                         lo.p, hi.p, inv4n * zh_inv[j], (size_t)n);
       NZ_HIP(hipGetLastError());
-      NZ_HIP(hipStreamSynchronize(s));
+      NZ_HIP(hipStreamSynchronize(s));  // lo / hi are reallocated by the next coset
     }
     for (int k = 0; k < 3; k++)
       NZ_HIP(hipMemcpy(sig_top[k], sigma.p + (size_t)k * 5 * n + (n - 4), 4 * sizeof(Fr), hipMemcpyDeviceToHost));
@@ -1310,7 +1322,7 @@ Prover::Prover(const uint8_t* zkey_bytes, size_t len, int device) {
       for (int j = 0; j < 3; j++) {
         NttIo io;
         io.in_len = n;
-        io.in_f = tw3.p + (size_t)j * n;
+        io.tw = ctw3.p + (size_t)j * (n - 1);
         ntt(eng->ntt_tables, coefs, out + (size_t)j * n, power, false, s, nullptr, &io);
       }
     };
@@ -1391,6 +1403,7 @@ void Prover::alloc_workspace() {
   const size_t ne = quot3 ? (size_t)3 * n : n4;
   A4.alloc(ne); B4.alloc(ne); C4.alloc(ne); Z4.alloc(ne);
   T.alloc(ne); Tz.alloc(ne); t.alloc(quot3 ? ne + 6 : n4);
+  if (quot3) bx_lo.alloc(4096);  // beta x_lo[i], per proof (k_beta_xlo)
   pol_r.alloc(n + 3); pol_wxi.alloc(n + 6); pol_wxiw.alloc(n + 3);
   blind.alloc(13);  // b1..b11 (index 0 unused), then the 32-bit check flags in slot 12
   // tile totals / heads (n / kTileN + 2) and the small scans' levels over them
@@ -1446,7 +1459,7 @@ Prover::Prover(const Prover& pk, int lane) {
   cq.alias(pk.cq); cs.alias(pk.cs); cl.alias(pk.cl);
   quot3 = pk.quot3;
   cq3.alias(pk.cq3); cs3.alias(pk.cs3); cl3.alias(pk.cl3);
-  tw3.alias(pk.tw3); itw3.alias(pk.itw3);
+  ctw3.alias(pk.ctw3); itw3.alias(pk.itw3);
   for (int j = 0; j < 3; j++) d3[j] = pk.d3[j];
   std::memcpy(sig_top, pk.sig_top, sizeof(sig_top));
   alloc_workspace();
@@ -1493,12 +1506,14 @@ void Prover::round3_quot3(const Fr& beta, const Fr& gamma, const Fr& alpha, hipS
   q29.bk1 = f29_exp(beta * k1, 5);
   q29.bk2 = f29_exp(beta * k2, 5);
   q29.alpha2 = f29_exp(alpha * alpha, 5);
-  for (int k = 0; k < 4; k++) q29.zhinv[k] = f29_exp(zh_inv[k], 5);
+  for (int k = 0; k < 4; k++) q29.zhinv[k] = f29_exp(zh_inv[k], 5);  // (unread: 1/Z_H is in itw3)
   q29.gamma = f29_exp(gamma, 0);
   q29.negone = f29_exp(neg(Fr::one()), 0);
   q29.alpha = f29_exp(alpha, 20);
+  if (q29.k23)
+    hipLaunchKernelGGL(k_beta_xlo, dim3(grid_for(4096, kT)), dim3(kT), 0, s, x_lo.p, q29.beta, (size_t)4096, bx_lo.p);
   hipLaunchKernelGGL((k_quotient_coset29<true>), dim3(grid_for(n3, kT, 1u << 30)), dim3(kT), 0, s, A4.p, B4.p, C4.p,
-                     Z4.p, cq3.p, cs3.p, cl3.p, nPublic, A.p, (size_t)n, x_lo.p, root_hi.p, q29, T.p);
+                     Z4.p, cq3.p, cs3.p, cl3.p, nPublic, A.p, (size_t)n, x_lo.p, root_hi.p, bx_lo.p, q29, T.p);
   if (!side) launch_gate_check(s);
   for (int j = 0; j < 3; j++) {  // v_j = (t mod (X^n - d_j)) / 4
     NttIo io;
@@ -1587,7 +1602,7 @@ void Prover::to4t_evals4(const Fr* coefs, Fr* evals4, int nb, hipStream_t s, uin
     for (int j = 0; j < 3; j++) {
       NttIo io;
       io.in_len = n;
-      io.in_f = tw3.p + (size_t)j * n;
+      io.tw = ctw3.p + (size_t)j * (n - 1);  // the twist c_j^k is in the twiddles
       io.fold_len = (size_t)nb;
       io.fold_n = n;
       io.fold_f = fr29_operand(d3[j]);
@@ -2115,7 +2130,8 @@ void Prover::prove(const uint8_t* witness, size_t n_witness, const uint8_t* blin
       q29.negone = f29_exp(neg(Fr::one()), 0);
       q29.alpha = f29_exp(alpha, 20);
       hipLaunchKernelGGL((k_quotient_coset29<false>), dim3(grid_for(n4, kT, 1u << 30)), dim3(kT), 0, s, A4.p, B4.p,
-                         C4.p, Z4.p, cq.p, cs.p, cl.p, nPublic, A.p, (size_t)n, x_lo.p, root_hi.p, q29, T.p);
+                         C4.p, Z4.p, cq.p, cs.p, cl.p, nPublic, A.p, (size_t)n, x_lo.p, root_hi.p, (const Fr*)nullptr, q29,
+                         T.p);
     } else {
       hipLaunchKernelGGL(k_quotient_coset, dim3(grid_for(n4, kT, 1u << 30)), dim3(kT), 0, s, A4.p, B4.p, C4.p,
                          Z4.p, cq.p, cs.p, cl.p, nPublic, A.p, (size_t)n, x_lo.p, root_hi.p, q, T.p);

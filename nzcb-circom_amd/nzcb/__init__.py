@@ -45,6 +45,7 @@ EXPORTED_SYMBOLS = [
     "nzcb_nzcp_witness_dev", "nzcb_synth_setup_ex", "nzcb_memcpy_d2d",
     "nzcb_plonk_setup", "nzcb_prove_batch_status", "nzcb_wprog_remap", "nzcb_prove_logged", "nzcb_memcpy_d2d_async",
     "nzcb_debug_guard_check", "nzcb_debug_guard_selftest", "nzcb_debug_inject_fault", "nzcb_debug_f29",
+    "nzcb_debug_ntt_coset",
     "nzcb_msm_table_create_lagrange",
     "nzcb_verify_batch", "nzcb_engine_g1_lincomb", "nzcb_engine_verify_batch", "nzcb_debug_verify_batch_timings",
     "nzcb_r1cs_create", "nzcb_r1cs_create_file", "nzcb_r1cs_info", "nzcb_r1cs_check", "nzcb_r1cs_destroy",
@@ -92,7 +93,7 @@ def guard_check(device: int = -1) -> int:
     return checked.value
 
 
-F29_WORDS = {1: (27, 9), 2: (54, 18), 3: (18, 9), 4: (36, 18), 5: (18, 18), 6: (36, 9)}
+F29_WORDS = {1: (27, 9), 2: (54, 18), 3: (18, 9), 4: (36, 18), 5: (18, 18), 6: (36, 9), 7: (10, 9)}
 
 
 def f29_check(op: int, words, device: int = 0):
@@ -216,6 +217,7 @@ def load(path: str | None = None):
         "nzcb_engine_create": (c_void_p, [c_int, c_int, c_size_t, POINTER(_Err)]),
         "nzcb_engine_destroy": (None, [c_void_p]),
         "nzcb_engine_ntt": (c_int, [c_void_p, u8p, u8p, c_int, c_int, POINTER(_Err)]),
+        "nzcb_debug_ntt_coset": (c_int, [c_void_p, u8p, u8p, c_int, u8p, c_int, POINTER(_Err)]),
         "nzcb_engine_msm": (c_int, [c_void_p, u8p, u8p, c_size_t, c_int, u8p, POINTER(_Err)]),
         "nzcb_dev_alloc": (c_void_p, [c_size_t]),
         "nzcb_dev_alloc_on": (c_void_p, [c_int, c_size_t]),
@@ -502,6 +504,19 @@ class Engine:
         out = _out(32 * n)
         err = _Err()
         _check(self.lib.nzcb_engine_ntt(self.h, _buf(data_lem), out, log_n, int(inverse), ctypes.byref(err)), err)
+        return bytes(out)
+
+    def ntt_coset(self, data_lem: bytes, log_n: int, c_lem: bytes) -> bytes:
+        """The forward transform on the coset c<w> through a per-coset twiddle table
+        (include/nzcb_internal.h nzcb_debug_ntt_coset): 2^log_n + fold coefficients in, the
+        fold <= 2^log_n ones past 2^log_n folded in with x^n = c^n; 2^log_n evaluations out."""
+        n = 1 << log_n
+        fold = len(data_lem) // 32 - n
+        assert len(data_lem) == 32 * (n + fold) and fold >= 0 and len(c_lem) == 32
+        out = _out(32 * n)
+        err = _Err()
+        _check(self.lib.nzcb_debug_ntt_coset(self.h, _buf(data_lem), out, log_n, _buf(c_lem), fold,
+                                             ctypes.byref(err)), err)
         return bytes(out)
 
     def msm(self, bases_lem: bytes, scalars: bytes, scalars_mont: bool = False) -> bytes:
