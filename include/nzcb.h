@@ -58,6 +58,8 @@ enum {
   NZCB_ERR_INTERNAL = 11
 };
 
+/* Every entry point that takes an nzcb_err* (NULL is allowed) and returns an int or a handle sets
+ * err->code on every return, 0 on success, and writes err->msg only on failure. */
 typedef struct nzcb_err {
   int code;
   char msg[256];

@@ -1,9 +1,4 @@
 // C-ABI: prover context, proofs and snarkjs-format JSON (include/nzcb.h).
-#include <fcntl.h>
-#include <sys/mman.h>
-#include <sys/stat.h>
-#include <unistd.h>
-
 #include <algorithm>
 #include <atomic>
 #include <condition_variable>
@@ -141,84 +136,46 @@ int copy_out(const std::string& s, char* out, size_t cap) {
   return 0;
 }
 
+std::unique_ptr<nzcb_ctx> new_ctx(const uint8_t* zkey, size_t zkey_len, int device) {
+  auto c = std::make_unique<nzcb_ctx>();
+  c->p.reset(new Prover(zkey, zkey_len, device));
+  c->reset_pool();
+  return c;
+}
+
+std::unique_ptr<nzcb_ctx> new_ctx_devices(const uint8_t* zkey, size_t zkey_len, const int* devices, int ndev) {
+  if (!devices || ndev < 1 || ndev > 64) throw Error(NZCB_ERR_ARG, "devices: 1..64 ids");
+  for (int i = 0; i < ndev; i++)
+    for (int j = 0; j < i; j++)
+      if (devices[i] == devices[j]) throw Error(NZCB_ERR_ARG, "devices: an id appears twice");
+  auto c = new_ctx(zkey, zkey_len, devices[0]);
+  for (int i = 1; i < ndev; i++) {
+    c->dev_p.emplace_back(new Prover(zkey, zkey_len, devices[i]));
+    c->dev_extra.emplace_back();
+  }
+  c->reset_pool();
+  NZ_HIP(hipSetDevice(devices[0]));
+  return c;
+}
+
 }  // namespace
 
 extern "C" {
 
 nzcb_ctx* nzcb_ctx_create(const uint8_t* zkey, size_t zkey_len, int device, nzcb_err* err) {
-  try {
-    auto* c = new nzcb_ctx();
-    c->p.reset(new Prover(zkey, zkey_len, device));
-    c->reset_pool();
-    if (err) err->code = 0;
-    return c;
-  } catch (const Error& e) {
-    set_err(err, e.code, e.what());
-  } catch (const std::exception& e) {
-    set_err(err, NZCB_ERR_INTERNAL, e.what());
-  }
-  return nullptr;
+  return guarded_new<nzcb_ctx>(err, [&] { return new_ctx(zkey, zkey_len, device); });
 }
 
 nzcb_ctx* nzcb_ctx_create_devices(const uint8_t* zkey, size_t zkey_len, const int* devices, int ndev, nzcb_err* err) {
-  if (!devices || ndev < 1 || ndev > 64) {
-    set_err(err, NZCB_ERR_ARG, "devices: 1..64 ids");
-    return nullptr;
-  }
-  for (int i = 0; i < ndev; i++)
-    for (int j = 0; j < i; j++)
-      if (devices[i] == devices[j]) {
-        set_err(err, NZCB_ERR_ARG, "devices: an id appears twice");
-        return nullptr;
-      }
-  nzcb_ctx* c = nzcb_ctx_create(zkey, zkey_len, devices[0], err);
-  if (!c) return nullptr;
-  try {
-    for (int i = 1; i < ndev; i++) {
-      c->dev_p.emplace_back(new Prover(zkey, zkey_len, devices[i]));
-      c->dev_extra.emplace_back();
-    }
-    c->reset_pool();
-    NZ_HIP(hipSetDevice(devices[0]));
-    if (err) err->code = 0;
-    return c;
-  } catch (const Error& e) {
-    set_err(err, e.code, e.what());
-  } catch (const std::exception& e) {
-    set_err(err, NZCB_ERR_INTERNAL, e.what());
-  }
-  delete c;
-  return nullptr;
+  return guarded_new<nzcb_ctx>(err, [&] { return new_ctx_devices(zkey, zkey_len, devices, ndev); });
 }
 
 nzcb_ctx* nzcb_ctx_create_file(const char* zkey_path, const int* devices, int ndev, nzcb_err* err) {
-  if (!zkey_path) {
-    set_err(err, NZCB_ERR_ARG, "null zkey path");
-    return nullptr;
-  }
-  const int fd = open(zkey_path, O_RDONLY);
-  if (fd < 0) {
-    set_err(err, NZCB_ERR_ARG, (std::string("cannot open ") + zkey_path).c_str());
-    return nullptr;
-  }
-  struct stat st;
-  if (fstat(fd, &st) != 0 || st.st_size <= 0) {
-    close(fd);
-    set_err(err, NZCB_ERR_FORMAT, "zkey file is empty");
-    return nullptr;
-  }
-  void* m = mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
-  close(fd);
-  if (m == MAP_FAILED) {
-    set_err(err, NZCB_ERR_INTERNAL, "mmap of the zkey failed");
-    return nullptr;
-  }
-  int dev0 = 0;
-  nzcb_ctx* c = devices && ndev > 0
-                    ? nzcb_ctx_create_devices(static_cast<const uint8_t*>(m), (size_t)st.st_size, devices, ndev, err)
-                    : nzcb_ctx_create(static_cast<const uint8_t*>(m), (size_t)st.st_size, dev0, err);
-  munmap(m, (size_t)st.st_size);
-  return c;
+  return guarded_new<nzcb_ctx>(err, [&] {
+    if (!zkey_path) throw Error(NZCB_ERR_ARG, "null zkey path");
+    const MappedFile f(zkey_path, "the zkey", "zkey file is empty");
+    return devices && ndev > 0 ? new_ctx_devices(f.data, f.size, devices, ndev) : new_ctx(f.data, f.size, 0);
+  });
 }
 
 int nzcb_ctx_devices(const nzcb_ctx* ctx) { return ctx ? 1 + (int)ctx->dev_p.size() : 0; }
@@ -240,13 +197,10 @@ void nzcb_ctx_set_transcript_public(nzcb_ctx* ctx, int on) {
 
 int nzcb_ctx_set_lanes(nzcb_ctx* ctx, int lanes, nzcb_err* err) {
   if (!ctx || lanes < 1 || lanes > 16) return fail(err, NZCB_ERR_ARG, "lanes must be in 1..16");
-  try {
+  return guarded(err, [&] {
     {  // unchanged: no exclusive lock, which would wait for every proof in flight
       std::shared_lock<std::shared_mutex> lk(ctx->cfg);
-      if (ctx->lanes() == (size_t)lanes) {
-        if (err) err->code = 0;
-        return 0;
-      }
+      if (ctx->lanes() == (size_t)lanes) return;
     }
     std::unique_lock<std::shared_mutex> lk(ctx->cfg);
     const size_t before = ctx->lanes();
@@ -289,46 +243,28 @@ int nzcb_ctx_set_lanes(nzcb_ctx* ctx, int lanes, nzcb_err* err) {
     }
     ctx->reset_pool();
     NZ_HIP(hipSetDevice(ctx->p->eng->device));
-    if (err) err->code = 0;
-    return 0;
-  } catch (const Error& e) {
-    return fail(err, e.code, e.what());
-  } catch (const std::exception& e) {
-    return fail(err, NZCB_ERR_INTERNAL, e.what());
-  }
+  });
 }
 
 int nzcb_ctx_lanes(const nzcb_ctx* ctx) { return ctx ? (int)ctx->lanes() : 0; }
 
 int nzcb_ctx_set_msm_devices(nzcb_ctx* ctx, const int* devices, int ndev, nzcb_err* err) {
   if (!ctx || !devices || ndev < 1 || ndev > 64) return fail(err, NZCB_ERR_ARG, "devices: 1..64 ids");
-  try {
+  return guarded(err, [&] {
     std::unique_lock<std::shared_mutex> lk(ctx->cfg);
     ctx->p->set_msm_devices(std::vector<int>(devices, devices + ndev));
     ctx->reset_pool();
-    if (err) err->code = 0;
-    return 0;
-  } catch (const Error& e) {
-    return fail(err, e.code, e.what());
-  } catch (const std::exception& e) {
-    return fail(err, NZCB_ERR_INTERNAL, e.what());
-  }
+  });
 }
 
 int nzcb_ctx_set_msm_split(nzcb_ctx* ctx, int world, size_t own_points, size_t own_lagrange,
                            nzcb_msm_send_fn send, nzcb_msm_gather_fn gather, void* user, nzcb_err* err) {
   if (!ctx || world < 1 || world > 1024) return fail(err, NZCB_ERR_ARG, "msm split: world must be in 1..1024");
-  try {
+  return guarded(err, [&] {
     std::unique_lock<std::shared_mutex> lk(ctx->cfg);
     ctx->p->set_msm_split(world, own_points, own_lagrange, send, gather, user);
     ctx->reset_pool();
-    if (err) err->code = 0;
-    return 0;
-  } catch (const Error& e) {
-    return fail(err, e.code, e.what());
-  } catch (const std::exception& e) {
-    return fail(err, NZCB_ERR_INTERNAL, e.what());
-  }
+  });
 }
 
 // keep_going: prove every item and report each one's code in status_out (SURVEY.md §5:
@@ -428,13 +364,13 @@ int prove_one(nzcb_ctx* ctx, const void* witness, size_t n, int kind, const uint
     return fail(err, NZCB_ERR_ARG, "unknown witness kind");
   if (pub_cap < 32 * (size_t)ctx->p->nPublic || (!pub_out && ctx->p->nPublic))
     return fail(err, NZCB_ERR_ARG, "public output buffer too small");
-  try {
+  return guarded(err, [&] {
     const uint8_t* values = (const uint8_t*)witness;
     size_t nw = n;
     if (kind == NZCB_WITNESS_WTNS) {
       Wtns w = parse_wtns(values, n);
       if (!w.q_is_r)
-        return fail(err, NZCB_ERR_CURVE, "Curve of the witness does not match the curve of the proving key");
+        throw Error(NZCB_ERR_CURVE, "Curve of the witness does not match the curve of the proving key");
       values = w.values;
       nw = w.nWitness;
     }
@@ -455,13 +391,7 @@ int prove_one(nzcb_ctx* ctx, const void* witness, size_t n, int kind, const uint
     pr->log = nullptr;
     ctx->release(pr);
     NZ_HIP(hipSetDevice(caller_dev));
-    if (err) err->code = 0;
-    return 0;
-  } catch (const Error& e) {
-    return fail(err, e.code, e.what());
-  } catch (const std::exception& e) {
-    return fail(err, NZCB_ERR_INTERNAL, e.what());
-  }
+  });
 }
 }  // namespace
 

@@ -4,21 +4,13 @@
 
 #include <cstdint>
 #include <cstdio>
-#include <stdexcept>
 #include <string>
 
 #include "../../include/nzcb_internal.h"
+#include "capi_guard.h"
 #include "field.h"
 
 namespace nzcb {
-
-struct Error : std::runtime_error {
-  int code;
-  Error(int c, const std::string& m) : std::runtime_error(m), code(c) {}
-};
-
-// Error codes: NZCB_* from include/nzcb.h. Fills `err` (may be NULL); capi_engine.hip.
-void set_err(nzcb_err* err, int code, const char* msg);
 
 // Kernel stores into pinned host memory (the prover's mailbox, the fixed-base MSM's window
 // sums; round 6): plain stores, then a system-scope fence before the wave ends, so the host

@@ -69,37 +69,23 @@ void launch(const uint32_t* in, uint32_t* out, size_t count) {
 using namespace nzcb;
 
 extern "C" int nzcb_debug_f29(int device, int op, const uint32_t* in, size_t count, uint32_t* out, nzcb_err* err) {
-  auto fail = [&](int code, const std::string& m) {
-    if (err) {
-      err->code = code;
-      std::snprintf(err->msg, sizeof(err->msg), "%s", m.c_str());
+  return guarded(err, [&] {
+    if (op < 1 || op > 7 || (count && (!in || !out)) || count > (size_t(1) << 24))
+      throw Error(NZCB_ERR_ARG, "f29 check: op 1..7, count <= 2^24");
+    if (!count) return;
+    NZ_HIP(hipSetDevice(device));
+    DevBuf<uint32_t> din(count * kIn[op]), dout(count * kOut[op]);
+    NZ_HIP(hipMemcpy(din.p, in, count * kIn[op] * 4, hipMemcpyHostToDevice));
+    switch (op) {
+      case 1: launch<1>(din.p, dout.p, count); break;
+      case 2: launch<2>(din.p, dout.p, count); break;
+      case 3: launch<3>(din.p, dout.p, count); break;
+      case 4: launch<4>(din.p, dout.p, count); break;
+      case 5: launch<5>(din.p, dout.p, count); break;
+      case 6: launch<6>(din.p, dout.p, count); break;
+      default: launch<7>(din.p, dout.p, count); break;
     }
-    return code;
-  };
-  if (op < 1 || op > 7 || (count && (!in || !out)) || count > (size_t(1) << 24))
-    return fail(NZCB_ERR_ARG, "f29 check: op 1..7, count <= 2^24");
-  try {
-    if (count) {
-      NZ_HIP(hipSetDevice(device));
-      DevBuf<uint32_t> din(count * kIn[op]), dout(count * kOut[op]);
-      NZ_HIP(hipMemcpy(din.p, in, count * kIn[op] * 4, hipMemcpyHostToDevice));
-      switch (op) {
-        case 1: launch<1>(din.p, dout.p, count); break;
-        case 2: launch<2>(din.p, dout.p, count); break;
-        case 3: launch<3>(din.p, dout.p, count); break;
-        case 4: launch<4>(din.p, dout.p, count); break;
-        case 5: launch<5>(din.p, dout.p, count); break;
-        case 6: launch<6>(din.p, dout.p, count); break;
-        default: launch<7>(din.p, dout.p, count); break;
-      }
-      NZ_HIP(hipGetLastError());
-      NZ_HIP(hipMemcpy(out, dout.p, count * kOut[op] * 4, hipMemcpyDeviceToHost));
-    }
-    if (err) err->code = 0;
-    return 0;
-  } catch (const Error& e) {
-    return fail(e.code, e.what());
-  } catch (const std::exception& e) {
-    return fail(NZCB_ERR_INTERNAL, e.what());
-  }
+    NZ_HIP(hipGetLastError());
+    NZ_HIP(hipMemcpy(out, dout.p, count * kOut[op] * 4, hipMemcpyDeviceToHost));
+  });
 }

@@ -559,6 +559,19 @@ void check_params(const nzcb_nzcp_params* p) {
     throw Error(NZCB_ERR_ARG, "nzcp: MaxCborMapLenVC must be in [0, 32]");
 }
 
+void witness_dev(int device, const nzcb_nzcp_params* prm, const void* dev_inputs, int count, void* dev_records,
+                 void* dev_witness, size_t witness_stride, void* stream) {
+  check_params(prm);
+  if (count < 0 || (count > 0 && !dev_inputs)) throw Error(NZCB_ERR_ARG, "nzcp: bad inputs");
+  if (dev_witness && witness_stride < 4 * 32) throw Error(NZCB_ERR_ARG, "nzcp: witness stride < 4 signals");
+  if (count == 0) return;
+  NZ_HIP(hipSetDevice(device));
+  hipLaunchKernelGGL(nzcp_witness_kernel, dim3(count), dim3(kThreads), 0, (hipStream_t)stream,
+                     (const uint8_t*)dev_inputs, count, *prm, (nzcb_nzcp_record*)dev_records, (uint8_t*)dev_witness,
+                     witness_stride);
+  NZ_HIP(hipGetLastError());
+}
+
 }  // namespace nzcp
 }  // namespace nzcb
 
@@ -573,48 +586,25 @@ size_t nzcb_nzcp_input_signals(const nzcb_nzcp_params* prm) {
 
 int nzcb_nzcp_witness_dev(int device, const nzcb_nzcp_params* prm, const void* dev_inputs, int count,
                           void* dev_records, void* dev_witness, size_t witness_stride, void* stream, nzcb_err* err) {
-  try {
-    nzcp::check_params(prm);
-    if (count < 0 || (count > 0 && !dev_inputs)) throw Error(NZCB_ERR_ARG, "nzcp: bad inputs");
-    if (dev_witness && witness_stride < 4 * 32) throw Error(NZCB_ERR_ARG, "nzcp: witness stride < 4 signals");
-    if (count == 0) return NZCB_OK;
-    NZ_HIP(hipSetDevice(device));
-    hipLaunchKernelGGL(nzcp::nzcp_witness_kernel, dim3(count), dim3(nzcp::kThreads), 0, (hipStream_t)stream,
-                       (const uint8_t*)dev_inputs, count, *prm, (nzcb_nzcp_record*)dev_records,
-                       (uint8_t*)dev_witness, witness_stride);
-    NZ_HIP(hipGetLastError());
-    return NZCB_OK;
-  } catch (const Error& e) {
-    set_err(err, e.code, e.what());
-    return e.code;
-  } catch (const std::exception& e) {
-    set_err(err, NZCB_ERR_INTERNAL, e.what());
-    return NZCB_ERR_INTERNAL;
-  }
+  return guarded(err, [&] {
+    nzcp::witness_dev(device, prm, dev_inputs, count, dev_records, dev_witness, witness_stride, stream);
+  });
 }
 
 int nzcb_nzcp_witness(int device, const nzcb_nzcp_params* prm, const uint8_t* inputs, int count,
                       nzcb_nzcp_record* records, nzcb_err* err) {
-  try {
+  return guarded(err, [&] {
     nzcp::check_params(prm);
     if (count < 0 || (count > 0 && (!inputs || !records))) throw Error(NZCB_ERR_ARG, "nzcp: bad buffers");
-    if (count == 0) return NZCB_OK;
+    if (count == 0) return;
     NZ_HIP(hipSetDevice(device));
     size_t in_bytes = nzcb_nzcp_input_signals(prm) * 32 * (size_t)count;
     DevBuf<uint8_t> din(in_bytes);
     DevBuf<nzcb_nzcp_record> drec((size_t)count);
     NZ_HIP(hipMemcpy(din.p, inputs, in_bytes, hipMemcpyHostToDevice));
-    int rc = nzcb_nzcp_witness_dev(device, prm, din.p, count, drec.p, nullptr, 0, nullptr, err);
-    if (rc) return rc;
+    nzcp::witness_dev(device, prm, din.p, count, drec.p, nullptr, 0, nullptr);
     NZ_HIP(hipMemcpy(records, drec.p, drec.bytes(), hipMemcpyDeviceToHost));
-    return NZCB_OK;
-  } catch (const Error& e) {
-    set_err(err, e.code, e.what());
-    return e.code;
-  } catch (const std::exception& e) {
-    set_err(err, NZCB_ERR_INTERNAL, e.what());
-    return NZCB_ERR_INTERNAL;
-  }
+  });
 }
 
 }  // extern "C"

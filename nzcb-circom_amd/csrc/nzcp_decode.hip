@@ -15,7 +15,7 @@
 #include <chrono>
 #include <vector>
 
-#include "common.h"
+#include "devcall.h"
 #include "nzcp_decode.h"
 
 namespace nzcb {
@@ -111,20 +111,6 @@ __global__ __launch_bounds__(kLanes) void k_nzcp_decode(const uint8_t* __restric
   for (uint32_t i = lane; i < kRecWords; i += kLanes) dst[i] = src[i];
 }
 
-struct DeviceScope {
-  int prev = -1;
-  explicit DeviceScope(int device) {
-    int ndev = 0;
-    NZ_HIP(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) throw Error(NZCB_ERR_ARG, "no such device");
-    NZ_HIP(hipGetDevice(&prev));
-    NZ_HIP(hipSetDevice(device));
-  }
-  ~DeviceScope() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
-
 // of the calling thread's last nzcb_nzcp_decode: kernel ms (0 on the host path), wall ms
 thread_local double g_times[2] = {0, 0};
 
@@ -194,54 +180,26 @@ void decode(int device, const uint8_t* uris, const uint32_t* offsets, int count,
     g_times[1] = wall();
     return;
   }
-  DeviceScope scope(device);
-  hipStream_t st = nullptr;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  DevBuf<uint8_t> d_uris(total), d_data(data20 ? kDataBytes * n : 0), d_inputs(in_bytes * n),
-      d_tbs(tbs_out ? tbs_stride * n : 0);
-  DevBuf<uint32_t> d_off(n + 1);
-  DevBuf<nzcb_nzcp_pass> d_pass(n);
-  struct Cleanup {
-    hipStream_t& st;
-    hipEvent_t (&ev)[2];
-    ~Cleanup() {
-      if (st) (void)hipStreamSynchronize(st);
-      for (auto& e : ev)
-        if (e) (void)hipEventDestroy(e);
-      if (st) (void)hipStreamDestroy(st);
-    }
-  } cleanup{st, ev};
-  NZ_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  for (auto& e : ev) NZ_HIP(hipEventCreate(&e));
-  if (total) NZ_HIP(hipMemcpyAsync(d_uris.p, uris, total, hipMemcpyHostToDevice, st));
-  NZ_HIP(hipMemcpyAsync(d_off.p, offsets, 4 * (n + 1), hipMemcpyHostToDevice, st));
-  if (data20) NZ_HIP(hipMemcpyAsync(d_data.p, data20, kDataBytes * n, hipMemcpyHostToDevice, st));
-  NZ_HIP(hipEventRecord(ev[0], st));
-  launch(d_uris.p, d_off.p, count, max_tbs, d_data.p, d_pass.p, d_inputs.p, d_tbs.p, tbs_stride, st);
-  NZ_HIP(hipEventRecord(ev[1], st));
-  NZ_HIP(hipMemcpyAsync(passes, d_pass.p, sizeof(nzcb_nzcp_pass) * n, hipMemcpyDeviceToHost, st));
-  if (inputs) NZ_HIP(hipMemcpyAsync(inputs, d_inputs.p, in_bytes * n, hipMemcpyDeviceToHost, st));
-  if (tbs_out && tbs_stride) NZ_HIP(hipMemcpyAsync(tbs_out, d_tbs.p, tbs_stride * n, hipMemcpyDeviceToHost, st));
-  NZ_HIP(hipStreamSynchronize(st));
-  float ms = 0;
-  NZ_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
-  g_times[0] = ms;
+  CallScope cs(device, nullptr, 2);
+  // the kernel takes a NULL data20, inputs or tbs_out as "not asked for"
+  uint8_t* d_uris = total ? cs.alloc<uint8_t>(total) : nullptr;
+  uint8_t* d_data = data20 ? cs.alloc<uint8_t>(kDataBytes * n) : nullptr;
+  uint8_t* d_inputs = inputs ? cs.alloc<uint8_t>(in_bytes * n) : nullptr;
+  uint8_t* d_tbs = tbs_out && tbs_stride ? cs.alloc<uint8_t>(tbs_stride * n) : nullptr;
+  uint32_t* d_off = cs.alloc<uint32_t>(4 * (n + 1));
+  nzcb_nzcp_pass* d_pass = cs.alloc<nzcb_nzcp_pass>(sizeof(nzcb_nzcp_pass) * n);
+  if (total) NZ_HIP(hipMemcpyAsync(d_uris, uris, total, hipMemcpyHostToDevice, cs.st));
+  NZ_HIP(hipMemcpyAsync(d_off, offsets, 4 * (n + 1), hipMemcpyHostToDevice, cs.st));
+  if (data20) NZ_HIP(hipMemcpyAsync(d_data, data20, kDataBytes * n, hipMemcpyHostToDevice, cs.st));
+  cs.record(0);
+  launch(d_uris, d_off, count, max_tbs, d_data, d_pass, d_inputs, d_tbs, tbs_stride, cs.st);
+  cs.record(1);
+  NZ_HIP(hipMemcpyAsync(passes, d_pass, sizeof(nzcb_nzcp_pass) * n, hipMemcpyDeviceToHost, cs.st));
+  if (inputs) NZ_HIP(hipMemcpyAsync(inputs, d_inputs, in_bytes * n, hipMemcpyDeviceToHost, cs.st));
+  if (d_tbs) NZ_HIP(hipMemcpyAsync(tbs_out, d_tbs, tbs_stride * n, hipMemcpyDeviceToHost, cs.st));
+  NZ_HIP(hipStreamSynchronize(cs.st));
+  g_times[0] = cs.elapsed(0, 1);
   g_times[1] = wall();
-}
-
-template <class F>
-int guarded(nzcb_err* err, F&& f) {
-  try {
-    f();
-    if (err) err->code = 0;
-    return 0;
-  } catch (const Error& e) {
-    set_err(err, e.code, e.what());
-    return e.code;
-  } catch (const std::exception& e) {
-    set_err(err, NZCB_ERR_INTERNAL, e.what());
-    return NZCB_ERR_INTERNAL;
-  }
 }
 
 }  // namespace
@@ -261,7 +219,7 @@ void nzcb_nzcp_pass_layout(uint32_t out[3]) {
 int nzcb_nzcp_decode(int device, const uint8_t* uris, const uint32_t* offsets, int count, const nzcb_nzcp_params* prm,
                      const uint8_t* data20, nzcb_nzcp_pass* passes_out, uint8_t* inputs_out, uint8_t* tbs_out,
                      size_t tbs_stride, nzcb_err* err) {
-  return nzdec::guarded(err, [&] {
+  return guarded(err, [&] {
     nzdec::decode(device, uris, offsets, count, prm, data20, passes_out, inputs_out, tbs_out, tbs_stride);
   });
 }
@@ -269,7 +227,7 @@ int nzcb_nzcp_decode(int device, const uint8_t* uris, const uint32_t* offsets, i
 int nzcb_nzcp_decode_dev(int device, const void* dev_uris, const void* dev_offsets, int count,
                          const nzcb_nzcp_params* prm, const void* dev_data20, void* dev_passes, void* dev_inputs,
                          void* dev_tbs, size_t tbs_stride, void* stream, nzcb_err* err) {
-  return nzdec::guarded(err, [&] {
+  return guarded(err, [&] {
     nzdec::decode_dev(device, dev_uris, dev_offsets, count, prm, dev_data20, dev_passes, dev_inputs, dev_tbs,
                       tbs_stride, stream);
   });

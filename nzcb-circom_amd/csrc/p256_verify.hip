@@ -19,7 +19,7 @@
 #include <cstring>
 #include <vector>
 
-#include "common.h"
+#include "devcall.h"
 #include "p256.h"
 
 namespace nzcb {
@@ -110,55 +110,6 @@ __global__ __launch_bounds__(kBlock) void k_p256_field(int op, int field_n, cons
   field_probe(op, field_n, a + size_t(32) * i, b + size_t(32) * i, out + size_t(32) * i);
 }
 
-struct DeviceScope {
-  int prev = -1;
-  explicit DeviceScope(int device) {
-    int ndev = 0;
-    NZ_HIP(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) throw Error(NZCB_ERR_ARG, "no such device");
-    NZ_HIP(hipGetDevice(&prev));
-    NZ_HIP(hipSetDevice(device));
-  }
-  ~DeviceScope() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
-
-// the call's stream (its own unless the caller gave one), events and buffers
-struct CallScope {
-  hipStream_t st = nullptr;
-  bool own = false;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  void* bufs[4] = {nullptr, nullptr, nullptr, nullptr};
-  explicit CallScope(void* stream) {
-    if (stream) {
-      st = static_cast<hipStream_t>(stream);
-    } else {
-      NZ_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-      own = true;
-    }
-    for (auto& e : ev) NZ_HIP(hipEventCreate(&e));
-  }
-  ~CallScope() {
-    if (st) (void)hipStreamSynchronize(st);
-    for (auto& b : bufs)
-      if (b) (void)hipFree(b);
-    for (auto& e : ev)
-      if (e) (void)hipEventDestroy(e);
-    if (own && st) (void)hipStreamDestroy(st);
-  }
-  template <class T>
-  T* alloc(int slot, size_t bytes) {
-    NZ_HIP(hipMalloc(&bufs[slot], bytes ? bytes : 4));
-    return static_cast<T*>(bufs[slot]);
-  }
-  float elapsed() {
-    float ms = 0;
-    NZ_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
-    return ms;
-  }
-};
-
 // of the calling thread: the last key's table build (kernel ms; wall ms on the host path), the
 // last verification's kernel ms and its wall ms
 thread_local double g_times[3] = {0, 0, 0};
@@ -173,21 +124,11 @@ double wall_ms(std::chrono::steady_clock::time_point t0) {
 using namespace nzcb;
 
 struct nzcb_p256_key {
-  int device = NZCB_P256_HOST;
   int w = kDefaultWindow;
-  std::vector<Affine> host;  // host path: G's table, then Q's
-  void* dev = nullptr;       // device path: the same, one allocation
+  std::vector<Affine> host;  // host path (dev.p is NULL): G's table, then Q's
+  DeviceBlock dev;           // device path: the same, one allocation
   const Affine* tg = nullptr;
   const Affine* tq = nullptr;
-  ~nzcb_p256_key() {
-    if (dev) {
-      int prev = 0;
-      if (hipGetDevice(&prev) == hipSuccess && hipSetDevice(device) == hipSuccess) {
-        (void)hipFree(dev);
-        (void)hipSetDevice(prev);
-      }
-    }
-  }
 };
 
 namespace nzcb {
@@ -202,7 +143,6 @@ void build(nzcb_p256_key& k, const uint8_t* pub_xy, int device, int w) {
   Affine q;
   q.x = to_mont<Fp>(x);
   q.y = to_mont<Fp>(y);
-  k.device = device;
   k.w = w;
   const int windows = table_windows(w);
   const size_t entries = table_entries(w);
@@ -221,39 +161,30 @@ void build(nzcb_p256_key& k, const uint8_t* pub_xy, int device, int w) {
     g_times[0] = wall_ms(t0);
     return;
   }
-  DeviceScope scope(device);
-  CallScope cs(nullptr);
-  NZ_HIP(hipMalloc(&k.dev, 2 * entries * sizeof(Affine)));
-  Affine* tab = static_cast<Affine*>(k.dev);
+  CallScope cs(device, nullptr, 2);
+  k.dev.alloc(2 * entries * sizeof(Affine));
+  Affine* tab = k.dev.at<Affine>(0);
   NZ_HIP(hipMemsetAsync(tab, 0, 2 * entries * sizeof(Affine), cs.st));  // the unused d = 0 slots
   const size_t tmp = (size_t(2) * windows) << w;
-  U256* zs = cs.alloc<U256>(0, tmp * sizeof(U256));
-  U256* prods = cs.alloc<U256>(1, tmp * sizeof(U256));
-  NZ_HIP(hipEventRecord(cs.ev[0], cs.st));
+  U256* zs = cs.alloc<U256>(tmp * sizeof(U256));
+  U256* prods = cs.alloc<U256>(tmp * sizeof(U256));
+  cs.record(0);
   k_p256_table<<<grid_for(2 * windows, kBlock), kBlock, 0, cs.st>>>(q, w, tab, tab + entries, zs, prods);
-  NZ_HIP(hipEventRecord(cs.ev[1], cs.st));
+  cs.record(1);
   NZ_HIP(hipGetLastError());
   NZ_HIP(hipStreamSynchronize(cs.st));
-  g_times[0] = cs.elapsed();
+  g_times[0] = cs.elapsed(0, 1);
   k.tg = tab;
   k.tq = tab + entries;
 }
 
 nzcb_p256_key* create(const uint8_t* pub_xy, int device, int w, nzcb_err* err) {
-  nzcb_p256_key* k = nullptr;
-  try {
+  return guarded_new<nzcb_p256_key>(err, [&] {
     if (!pub_xy) throw Error(NZCB_ERR_ARG, "null argument");
-    k = new nzcb_p256_key();
+    auto k = std::make_unique<nzcb_p256_key>();
     build(*k, pub_xy, device, w ? w : kDefaultWindow);
-    if (err) err->code = 0;
     return k;
-  } catch (const Error& e) {
-    set_err(err, e.code, e.what());
-  } catch (const std::exception& e) {
-    set_err(err, NZCB_ERR_INTERNAL, e.what());
-  }
-  delete k;
-  return nullptr;
+  });
 }
 
 void verify(nzcb_p256_key* k, const uint8_t* hashes, size_t hash_stride, const uint8_t* sigs, size_t sig_stride,
@@ -265,7 +196,7 @@ void verify(nzcb_p256_key* k, const uint8_t* hashes, size_t hash_stride, const u
   if (hash_stride < 32) throw Error(NZCB_ERR_ARG, "hash stride is shorter than a hash");
   if (sig_stride < 64) throw Error(NZCB_ERR_ARG, "signature stride is shorter than a signature");
   const auto t0 = std::chrono::steady_clock::now();
-  if (k->device == NZCB_P256_HOST) {
+  if (!k->dev.p) {
     if (on_device) throw Error(NZCB_ERR_ARG, "a host key object cannot read device buffers");
     for (int i = 0; i < count; i++)
       status_out[i] = verify_one(k->tg, k->tq, k->w, hashes + hash_stride * (size_t)i, sigs + sig_stride * (size_t)i);
@@ -275,10 +206,9 @@ void verify(nzcb_p256_key* k, const uint8_t* hashes, size_t hash_stride, const u
   if (on_device && ((reinterpret_cast<uintptr_t>(hashes) | reinterpret_cast<uintptr_t>(sigs) | hash_stride |
                      sig_stride) & 3))
     throw Error(NZCB_ERR_ARG, "device hashes, signatures and their strides must be multiples of 4");
-  DeviceScope scope(k->device);
-  CallScope cs(stream);
+  CallScope cs(k->dev.device, stream, 2);
   const size_t n = (size_t)count;
-  int32_t* d_status = cs.alloc<int32_t>(0, 4 * n);
+  int32_t* d_status = cs.alloc<int32_t>(4 * n);
   if (!on_device) {
     // packed on the host, one copy each
     std::vector<uint8_t> hp, sp;
@@ -294,8 +224,8 @@ void verify(nzcb_p256_key* k, const uint8_t* hashes, size_t hash_stride, const u
       for (size_t i = 0; i < n; i++) std::memcpy(&sp[64 * i], sigs + sig_stride * i, 64);
       ssrc = sp.data();
     }
-    uint8_t* d_h = cs.alloc<uint8_t>(1, 32 * n);
-    uint8_t* d_s = cs.alloc<uint8_t>(2, 64 * n);
+    uint8_t* d_h = cs.alloc<uint8_t>(32 * n);
+    uint8_t* d_s = cs.alloc<uint8_t>(64 * n);
     NZ_HIP(hipMemcpyAsync(d_h, hsrc, 32 * n, hipMemcpyHostToDevice, cs.st));
     NZ_HIP(hipMemcpyAsync(d_s, ssrc, 64 * n, hipMemcpyHostToDevice, cs.st));
     NZ_HIP(hipStreamSynchronize(cs.st));  // hp, sp leave scope
@@ -304,14 +234,14 @@ void verify(nzcb_p256_key* k, const uint8_t* hashes, size_t hash_stride, const u
     hash_stride = 32;
     sig_stride = 64;
   }
-  NZ_HIP(hipEventRecord(cs.ev[0], cs.st));
+  cs.record(0);
   k_p256_verify<<<grid_for(n, kBlock, 1u << 26), kBlock, 0, cs.st>>>(k->tg, k->tq, k->w, hashes, hash_stride, sigs,
                                                                      sig_stride, (uint32_t)n, d_status);
-  NZ_HIP(hipEventRecord(cs.ev[1], cs.st));
+  cs.record(1);
   NZ_HIP(hipGetLastError());
   NZ_HIP(hipMemcpyAsync(status_out, d_status, 4 * n, hipMemcpyDeviceToHost, cs.st));
   NZ_HIP(hipStreamSynchronize(cs.st));
-  g_times[1] = cs.elapsed();
+  g_times[1] = cs.elapsed(0, 1);
   g_times[2] = wall_ms(t0);
 }
 
@@ -319,15 +249,14 @@ void mul2_call(nzcb_p256_key* k, const uint8_t* u1, const uint8_t* u2, size_t co
   if (!k || count > kMaxProbe) throw Error(NZCB_ERR_ARG, "bad argument");
   if (!count) return;
   if (!u1 || !u2 || !out) throw Error(NZCB_ERR_ARG, "null argument");
-  if (k->device == NZCB_P256_HOST) {
+  if (!k->dev.p) {
     for (size_t i = 0; i < count; i++) mul2_affine(k->tg, k->tq, k->w, u1 + 32 * i, u2 + 32 * i, out + 64 * i);
     return;
   }
-  DeviceScope scope(k->device);
-  CallScope cs(nullptr);
-  uint8_t* d1 = cs.alloc<uint8_t>(0, 32 * count);
-  uint8_t* d2 = cs.alloc<uint8_t>(1, 32 * count);
-  uint8_t* d_out = cs.alloc<uint8_t>(2, 64 * count);
+  CallScope cs(k->dev.device, nullptr, 0);
+  uint8_t* d1 = cs.alloc<uint8_t>(32 * count);
+  uint8_t* d2 = cs.alloc<uint8_t>(32 * count);
+  uint8_t* d_out = cs.alloc<uint8_t>(64 * count);
   NZ_HIP(hipMemcpyAsync(d1, u1, 32 * count, hipMemcpyHostToDevice, cs.st));
   NZ_HIP(hipMemcpyAsync(d2, u2, 32 * count, hipMemcpyHostToDevice, cs.st));
   k_p256_mul2<<<grid_for(count, kBlock, 1u << 26), kBlock, 0, cs.st>>>(k->tg, k->tq, k->w, d1, d2, (uint32_t)count,
@@ -350,32 +279,16 @@ void field_call(int device, int op, int field, const uint8_t* a, const uint8_t* 
     for (size_t i = 0; i < count; i++) field_probe(op, field, a + 32 * i, b + 32 * i, out + 32 * i);
     return;
   }
-  DeviceScope scope(device);
-  CallScope cs(nullptr);
-  uint8_t* da = cs.alloc<uint8_t>(0, 32 * count);
-  uint8_t* db = cs.alloc<uint8_t>(1, 32 * count);
-  uint8_t* d_out = cs.alloc<uint8_t>(2, 32 * count);
+  CallScope cs(device, nullptr, 0);
+  uint8_t* da = cs.alloc<uint8_t>(32 * count);
+  uint8_t* db = cs.alloc<uint8_t>(32 * count);
+  uint8_t* d_out = cs.alloc<uint8_t>(32 * count);
   NZ_HIP(hipMemcpyAsync(da, a, 32 * count, hipMemcpyHostToDevice, cs.st));
   NZ_HIP(hipMemcpyAsync(db, b, 32 * count, hipMemcpyHostToDevice, cs.st));
   k_p256_field<<<grid_for(count, kBlock, 1u << 26), kBlock, 0, cs.st>>>(op, field, da, db, (uint32_t)count, d_out);
   NZ_HIP(hipGetLastError());
   NZ_HIP(hipMemcpyAsync(out, d_out, 32 * count, hipMemcpyDeviceToHost, cs.st));
   NZ_HIP(hipStreamSynchronize(cs.st));
-}
-
-template <class F>
-int guarded(nzcb_err* err, F&& f) {
-  try {
-    f();
-    if (err) err->code = 0;
-    return 0;
-  } catch (const Error& e) {
-    set_err(err, e.code, e.what());
-    return e.code;
-  } catch (const std::exception& e) {
-    set_err(err, NZCB_ERR_INTERNAL, e.what());
-    return NZCB_ERR_INTERNAL;
-  }
 }
 
 }  // namespace

@@ -34,17 +34,12 @@
 //
 // A call owns its stream (unless the caller passes one) and its device buffers and needs no
 // prover context; it may run while a context proves on the same device.
-#include <fcntl.h>
-#include <sys/mman.h>
-#include <sys/stat.h>
-#include <unistd.h>
-
 #include <algorithm>
 #include <cstring>
 #include <map>
 #include <vector>
 
-#include "common.h"
+#include "devcall.h"
 #include "r1cs_reader.h"
 #include "zkey.h"
 
@@ -253,42 +248,6 @@ __global__ __launch_bounds__(kRowBlock) void k_r1cs_collect(const unsigned long 
   }
 }
 
-struct DeviceScope {
-  int prev = -1;
-  explicit DeviceScope(int device) {
-    NZ_HIP(hipGetDevice(&prev));
-    NZ_HIP(hipSetDevice(device));
-  }
-  ~DeviceScope() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
-
-// the call's stream (its own unless the caller gave one), events and buffers
-struct CallScope {
-  hipStream_t st = nullptr;
-  bool own = false;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  void* bufs[4] = {nullptr, nullptr, nullptr, nullptr};
-  explicit CallScope(void* stream) {
-    if (stream) {
-      st = static_cast<hipStream_t>(stream);
-    } else {
-      NZ_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-      own = true;
-    }
-    for (auto& e : ev) NZ_HIP(hipEventCreate(&e));
-  }
-  ~CallScope() {
-    if (st) (void)hipStreamSynchronize(st);
-    for (auto& b : bufs)
-      if (b) (void)hipFree(b);
-    for (auto& e : ev)
-      if (e) (void)hipEventDestroy(e);
-    if (own && st) (void)hipStreamDestroy(st);
-  }
-};
-
 // kernel milliseconds of the calling thread's last device check: rows, long rows, collect
 thread_local double g_times[3] = {0, 0, 0};
 
@@ -299,24 +258,14 @@ thread_local double g_times[3] = {0, 0, 0};
 using namespace nzcb;
 
 struct nzcb_r1cs {
-  int device = NZCB_R1CS_HOST;
   uint32_t n_wires = 0, n_out = 0, n_pub_in = 0, n_prv_in = 0, n_cons = 0, n_terms = 0;
   uint32_t threshold = kLongRowThreshold, n_long = 0;
   int tile = kWitnessTile;  // the largest witness tile used: 4 means 4, then 2, then 1 for the rest
-  // host path: the arrays; device path: one allocation holding them
+  // host path (dev.p is NULL): the arrays; device path: one allocation holding them
   std::vector<uint32_t> ptr, wire, cid, long_rows;
   std::vector<Fr> coef;
-  void* dev = nullptr;
+  DeviceBlock dev;
   R1csView view{};
-  ~nzcb_r1cs() {
-    if (dev) {
-      int prev = 0;
-      if (hipGetDevice(&prev) == hipSuccess && hipSetDevice(device) == hipSuccess) {
-        (void)hipFree(dev);
-        (void)hipSetDevice(prev);
-      }
-    }
-  }
 };
 
 namespace nzcb {
@@ -333,7 +282,6 @@ void build(nzcb_r1cs& r, const uint8_t* d, size_t len, int device, uint32_t thre
   // holds is truncated, before anything is sized by it
   if ((uint64_t)f.n_cons * 12 > f.constraints.left) throw Error(NZCB_ERR_FORMAT, "r1cs: truncated");
   if (f.n_cons >= (1u << 31)) throw Error(NZCB_ERR_FORMAT, "r1cs: too many constraints");
-  r.device = device;
   r.n_wires = f.n_wires;
   r.n_out = f.n_out;
   r.n_pub_in = f.n_pub_in;
@@ -374,27 +322,22 @@ void build(nzcb_r1cs& r, const uint8_t* d, size_t len, int device, uint32_t thre
   r.view = R1csView{r.ptr.data(), r.wire.data(), r.cid.data(), r.coef.data(), r.long_rows.data(),
                     r.n_cons, r.n_long, r.threshold};
   if (device == NZCB_R1CS_HOST) return;
-  int ndev = 0;
-  NZ_HIP(hipGetDeviceCount(&ndev));
-  if (device < 0 || device >= ndev) throw Error(NZCB_ERR_ARG, "no such device");
   DeviceScope scope(device);
-  auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
-  const size_t o_ptr = 0, o_wire = o_ptr + up(4 * r.ptr.size()), o_cid = o_wire + up(4 * r.wire.size()),
-               o_coef = o_cid + up(4 * r.cid.size()), o_long = o_coef + up(32 * r.coef.size()),
-               total = o_long + up(4 * r.long_rows.size());
-  NZ_HIP(hipMalloc(&r.dev, total ? total : 256));
-  char* b = static_cast<char*>(r.dev);
+  BlockLayout lay;
+  const size_t o_ptr = lay.take(4 * r.ptr.size()), o_wire = lay.take(4 * r.wire.size()),
+               o_cid = lay.take(4 * r.cid.size()), o_coef = lay.take(32 * r.coef.size()),
+               o_long = lay.take(4 * r.long_rows.size());
+  r.dev.alloc(lay.total);  // never 0: ptr and coef are not empty
   auto put = [&](size_t off, const void* src, size_t bytes) {
-    if (bytes) NZ_HIP(hipMemcpy(b + off, src, bytes, hipMemcpyHostToDevice));
+    if (bytes) NZ_HIP(hipMemcpy(r.dev.p + off, src, bytes, hipMemcpyHostToDevice));
   };
   put(o_ptr, r.ptr.data(), 4 * r.ptr.size());
   put(o_wire, r.wire.data(), 4 * r.wire.size());
   put(o_cid, r.cid.data(), 4 * r.cid.size());
   put(o_coef, r.coef.data(), 32 * r.coef.size());
   put(o_long, r.long_rows.data(), 4 * r.long_rows.size());
-  r.view = R1csView{reinterpret_cast<const uint32_t*>(b + o_ptr), reinterpret_cast<const uint32_t*>(b + o_wire),
-                    reinterpret_cast<const uint32_t*>(b + o_cid), reinterpret_cast<const Fr*>(b + o_coef),
-                    reinterpret_cast<const uint32_t*>(b + o_long), r.n_cons, r.n_long, r.threshold};
+  r.view = R1csView{r.dev.at<uint32_t>(o_ptr), r.dev.at<uint32_t>(o_wire), r.dev.at<uint32_t>(o_cid),
+                    r.dev.at<Fr>(o_coef), r.dev.at<uint32_t>(o_long), r.n_cons, r.n_long, r.threshold};
   // the device object keeps no host copy of the matrices
   for (auto* vec : {&r.ptr, &r.wire, &r.cid, &r.long_rows}) std::vector<uint32_t>().swap(*vec);
   std::vector<Fr>().swap(r.coef);
@@ -466,28 +409,17 @@ void check_device(const nzcb_r1cs& r, const uint8_t* wit, size_t stride, bool on
     }
     return;
   }
-  DeviceScope scope(r.device);
-  CallScope cs(stream);
+  CallScope cs(r.dev.device, stream, 4);
   const uint32_t words = (r.n_cons + 63) / 64;
   const size_t wbytes = size_t(32) * r.n_wires;
   // witnesses per pass: the bitmap, the lists and (host witnesses) the staging buffer within the
   // budget; a tile count must fit grid.y
   size_t per = size_t(8) * words + size_t(4) * dcap + (on_device ? 0 : wbytes);
   const uint32_t chunk = (uint32_t)std::min<size_t>({(size_t)count, std::max<size_t>(1, kChunkBytes / per), 65532});
-  unsigned long long* d_bitmap = nullptr;
-  nzcb_r1cs_result* d_res = nullptr;
-  uint32_t* d_bad = nullptr;
-  uint8_t* d_wit = nullptr;
-  NZ_HIP(hipMalloc(&cs.bufs[0], size_t(8) * words * chunk));
-  d_bitmap = static_cast<unsigned long long*>(cs.bufs[0]);
-  NZ_HIP(hipMalloc(&cs.bufs[1], sizeof(nzcb_r1cs_result) * chunk));
-  d_res = static_cast<nzcb_r1cs_result*>(cs.bufs[1]);
-  NZ_HIP(hipMalloc(&cs.bufs[2], std::max<size_t>(4, size_t(4) * dcap * chunk)));
-  d_bad = static_cast<uint32_t*>(cs.bufs[2]);
-  if (!on_device) {
-    NZ_HIP(hipMalloc(&cs.bufs[3], wbytes * chunk));
-    d_wit = static_cast<uint8_t*>(cs.bufs[3]);
-  }
+  auto* d_bitmap = cs.alloc<unsigned long long>(size_t(8) * words * chunk);
+  auto* d_res = cs.alloc<nzcb_r1cs_result>(sizeof(nzcb_r1cs_result) * chunk);
+  uint32_t* d_bad = cs.alloc<uint32_t>(size_t(4) * dcap * chunk);
+  uint8_t* d_wit = on_device ? nullptr : cs.alloc<uint8_t>(wbytes * chunk);
   std::vector<uint32_t> lists(bad_out && dcap < cap ? size_t(dcap) * chunk : 0);
   for (uint32_t done = 0; done < (uint32_t)count; done += chunk) {
     const uint32_t n = std::min(chunk, (uint32_t)count - done);
@@ -503,13 +435,13 @@ void check_device(const nzcb_r1cs& r, const uint8_t* wit, size_t stride, bool on
       src = d_wit;
       src_stride = wbytes;
     }
-    NZ_HIP(hipEventRecord(cs.ev[0], cs.st));
+    cs.record(0);
     launch_rows(r, src, src_stride, n, d_bitmap, words, cs.st, false);
-    NZ_HIP(hipEventRecord(cs.ev[1], cs.st));
+    cs.record(1);
     if (r.n_long) launch_rows(r, src, src_stride, n, d_bitmap, words, cs.st, true);
-    NZ_HIP(hipEventRecord(cs.ev[2], cs.st));
+    cs.record(2);
     k_r1cs_collect<<<n, kRowBlock, 0, cs.st>>>(d_bitmap, words, d_res, d_bad, bad_out ? dcap : 0u);
-    NZ_HIP(hipEventRecord(cs.ev[3], cs.st));
+    cs.record(3);
     NZ_HIP(hipGetLastError());
     NZ_HIP(hipMemcpyAsync(results + done, d_res, sizeof(nzcb_r1cs_result) * n, hipMemcpyDeviceToHost, cs.st));
     if (bad_out && dcap) {
@@ -523,11 +455,7 @@ void check_device(const nzcb_r1cs& r, const uint8_t* wit, size_t stride, bool on
         std::memcpy(row, lists.data() + size_t(dcap) * i, size_t(4) * dcap);
         fill_bad(row, dcap, cap);
       }
-    for (int e = 0; e < 3; e++) {
-      float ms = 0;
-      NZ_HIP(hipEventElapsedTime(&ms, cs.ev[e], cs.ev[e + 1]));
-      g_times[e] += ms;
-    }
+    for (int e = 0; e < 3; e++) g_times[e] += cs.elapsed(e, e + 1);
   }
 }
 
@@ -554,7 +482,7 @@ void check(nzcb_r1cs* r, const void* witness, size_t n, int kind, int count, siz
   if (stride < wbytes) throw Error(NZCB_ERR_ARG, "witness stride is shorter than a witness");
   if (!bad_out) cap = 0;
   const bool on_device = kind == NZCB_WITNESS_DEVICE;
-  if (r->device == NZCB_R1CS_HOST) {
+  if (!r->dev.p) {
     if (on_device) throw Error(NZCB_ERR_ARG, "a host r1cs object cannot read device witnesses");
     check_host(*r, values, stride, count, results, bad_out, cap);
     return;
@@ -565,20 +493,12 @@ void check(nzcb_r1cs* r, const void* witness, size_t n, int kind, int count, siz
 }
 
 nzcb_r1cs* create(const uint8_t* d, size_t len, int device, uint32_t threshold, int tile, nzcb_err* err) {
-  nzcb_r1cs* r = nullptr;
-  try {
+  return guarded_new<nzcb_r1cs>(err, [&] {
     if (!d) throw Error(NZCB_ERR_ARG, "null argument");
-    r = new nzcb_r1cs();
+    auto r = std::make_unique<nzcb_r1cs>();
     build(*r, d, len, device, threshold, tile);
-    if (err) err->code = 0;
     return r;
-  } catch (const Error& e) {
-    set_err(err, e.code, e.what());
-  } catch (const std::exception& e) {
-    set_err(err, NZCB_ERR_INTERNAL, e.what());
-  }
-  delete r;
-  return nullptr;
+  });
 }
 
 }  // namespace
@@ -596,31 +516,13 @@ nzcb_r1cs* nzcb_r1cs_create(const uint8_t* r1cs, size_t len, int device, nzcb_er
 }
 
 nzcb_r1cs* nzcb_r1cs_create_file(const char* path, int device, nzcb_err* err) {
-  if (!path) {
-    set_err(err, NZCB_ERR_ARG, "null r1cs path");
-    return nullptr;
-  }
-  const int fd = open(path, O_RDONLY);
-  struct stat st;
-  if (fd < 0 || fstat(fd, &st) != 0) {
-    if (fd >= 0) close(fd);
-    set_err(err, NZCB_ERR_ARG, (std::string("cannot open ") + path).c_str());
-    return nullptr;
-  }
-  if (st.st_size == 0) {
-    close(fd);
-    set_err(err, NZCB_ERR_FORMAT, "r1cs: invalid file format");
-    return nullptr;
-  }
-  void* m = mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
-  close(fd);
-  if (m == MAP_FAILED) {
-    set_err(err, NZCB_ERR_INTERNAL, "mmap of the r1cs failed");
-    return nullptr;
-  }
-  nzcb_r1cs* r = create(static_cast<const uint8_t*>(m), (size_t)st.st_size, device, 0, 0, err);
-  munmap(m, (size_t)st.st_size);
-  return r;
+  return guarded_new<nzcb_r1cs>(err, [&] {
+    if (!path) throw Error(NZCB_ERR_ARG, "null r1cs path");
+    const MappedFile f(path, "the r1cs", "r1cs: invalid file format");
+    auto r = std::make_unique<nzcb_r1cs>();
+    build(*r, f.data, f.size, device, 0, 0);
+    return r;
+  });
 }
 
 int nzcb_r1cs_info(const nzcb_r1cs* r, uint32_t info[8]) {
@@ -638,17 +540,9 @@ int nzcb_r1cs_info(const nzcb_r1cs* r, uint32_t info[8]) {
 
 int nzcb_r1cs_check(nzcb_r1cs* r, const void* witness, size_t n, int kind, int count, size_t witness_stride,
                     nzcb_r1cs_result* results, uint32_t* bad_out, uint32_t bad_cap, void* stream, nzcb_err* err) {
-  try {
+  return guarded(err, [&] {
     check(r, witness, n, kind, count, witness_stride, results, bad_out, bad_cap, stream);
-    if (err) err->code = 0;
-    return 0;
-  } catch (const Error& e) {
-    set_err(err, e.code, e.what());
-    return e.code;
-  } catch (const std::exception& e) {
-    set_err(err, NZCB_ERR_INTERNAL, e.what());
-    return NZCB_ERR_INTERNAL;
-  }
+  });
 }
 
 int nzcb_debug_r1cs_check_timings(double* ms, int cap) {

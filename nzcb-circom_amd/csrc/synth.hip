@@ -21,7 +21,6 @@
 #include "r1cs_reader.h"
 
 namespace nzcb {
-void set_err(nzcb_err* err, int code, const char* msg);
 
 namespace {
 
@@ -694,43 +693,23 @@ static void ptau_synth(int power, const uint8_t* tau_le, int device, uint8_t** o
 extern "C" int nzcb_ptau_synth(int power, const uint8_t* tau, int device, uint8_t** ptau_out, size_t* ptau_len,
                                nzcb_err* err) {
   using namespace nzcb;
-  if (!tau || !ptau_out || !ptau_len) {
-    set_err(err, NZCB_ERR_ARG, "null argument");
-    return NZCB_ERR_ARG;
-  }
-  try {
+  return guarded(err, [&] {
+    if (!tau || !ptau_out || !ptau_len) throw Error(NZCB_ERR_ARG, "null argument");
     NZ_HIP(hipSetDevice(device));
     ptau_synth(power, tau, device, ptau_out, ptau_len);
-    return 0;
-  } catch (const Error& e) {
-    set_err(err, e.code, e.what());
-    return e.code;
-  } catch (const std::exception& e) {
-    set_err(err, NZCB_ERR_INTERNAL, e.what());
-    return NZCB_ERR_INTERNAL;
-  }
+  });
 }
 
 extern "C" int nzcb_synth_setup_ex(int power, int n_public, int n_inputs, uint64_t seed, uint32_t n_constraints,
                                    uint32_t flags, const uint8_t* tau, int device, uint8_t** zkey_out,
                                    size_t* zkey_len, uint8_t** wtns_out, size_t* wtns_len, nzcb_err* err) {
   using namespace nzcb;
-  if (!tau || !zkey_out || !zkey_len || !wtns_out || !wtns_len) {
-    set_err(err, NZCB_ERR_ARG, "null argument");
-    return NZCB_ERR_ARG;
-  }
-  try {
+  return guarded(err, [&] {
+    if (!tau || !zkey_out || !zkey_len || !wtns_out || !wtns_len) throw Error(NZCB_ERR_ARG, "null argument");
     NZ_HIP(hipSetDevice(device));
     synth_setup(power, n_public, n_inputs, seed, n_constraints, flags, tau, device, zkey_out, zkey_len, wtns_out,
                 wtns_len);
-    return 0;
-  } catch (const Error& e) {
-    set_err(err, e.code, e.what());
-    return e.code;
-  } catch (const std::exception& e) {
-    set_err(err, NZCB_ERR_INTERNAL, e.what());
-    return NZCB_ERR_INTERNAL;
-  }
+  });
 }
 
 extern "C" int nzcb_synth_setup(int power, int n_public, int n_inputs, uint64_t seed, uint32_t n_constraints,
@@ -743,19 +722,9 @@ extern "C" int nzcb_synth_setup(int power, int n_public, int n_inputs, uint64_t 
 extern "C" int nzcb_plonk_setup(const uint8_t* r1cs, size_t r1cs_len, const uint8_t* ptau, size_t ptau_len,
                                 int device, uint8_t** zkey_out, size_t* zkey_len, nzcb_err* err) {
   using namespace nzcb;
-  if (!r1cs || !ptau || !zkey_out || !zkey_len) {
-    set_err(err, NZCB_ERR_ARG, "null argument");
-    return NZCB_ERR_ARG;
-  }
-  try {
+  return guarded(err, [&] {
+    if (!r1cs || !ptau || !zkey_out || !zkey_len) throw Error(NZCB_ERR_ARG, "null argument");
     NZ_HIP(hipSetDevice(device));
     plonk_setup(r1cs, r1cs_len, ptau, ptau_len, device, zkey_out, zkey_len);
-    return 0;
-  } catch (const Error& e) {
-    set_err(err, e.code, e.what());
-    return e.code;
-  } catch (const std::exception& e) {
-    set_err(err, NZCB_ERR_INTERNAL, e.what());
-    return NZCB_ERR_INTERNAL;
-  }
+  });
 }

@@ -14,11 +14,6 @@
 // D-type twist (x, y) -> (x w^2, y w^3), Miller loop over 6x + 2 with affine Fq2 steps
 // and sparse lines, Frobenius corrections, and the exponent (p^12 - 1)/r. The CPU
 // oracle oracle/pairing.py states the same algorithm; tests/test_verify.py pins both.
-#include <fcntl.h>
-#include <sys/mman.h>
-#include <sys/stat.h>
-#include <unistd.h>
-
 #include <cstring>
 #include <string>
 #include <vector>
@@ -469,48 +464,22 @@ using namespace nzcb;
 extern "C" {
 
 int nzcb_vk_from_zkey(const uint8_t* zkey, size_t zkey_len, uint8_t* vk_out, nzcb_err* err) {
-  try {
+  return guarded(err, [&] {
     if (!zkey || !vk_out) throw Error(NZCB_ERR_ARG, "null argument");
     const Zkey z = parse_zkey(zkey, zkey_len);
     vk_write(z, vk_out);
-    if (err) err->code = 0;
-    return 0;
-  } catch (const Error& e) {
-    set_err(err, e.code, e.what());
-    return e.code;
-  } catch (const std::exception& e) {
-    set_err(err, NZCB_ERR_INTERNAL, e.what());
-    return NZCB_ERR_INTERNAL;
-  }
+  });
 }
 
 // the same from a zkey file, memory-mapped (a nzcp_live zkey is ~3.9 GB: larger than a
 // Node Buffer, so `zkey export verificationkey|solidityverifier` read it through here)
 int nzcb_vk_from_zkey_file(const char* zkey_path, uint8_t* vk_out, nzcb_err* err) {
-  if (!zkey_path || !vk_out) {
-    set_err(err, NZCB_ERR_ARG, "null argument");
-    return NZCB_ERR_ARG;
-  }
-  const int fd = open(zkey_path, O_RDONLY);
-  if (fd < 0) {
-    set_err(err, NZCB_ERR_ARG, (std::string("cannot open ") + zkey_path).c_str());
-    return NZCB_ERR_ARG;
-  }
-  struct stat st;
-  if (fstat(fd, &st) != 0 || st.st_size <= 0) {
-    close(fd);
-    set_err(err, NZCB_ERR_FORMAT, "zkey file is empty");
-    return NZCB_ERR_FORMAT;
-  }
-  void* m = mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
-  close(fd);
-  if (m == MAP_FAILED) {
-    set_err(err, NZCB_ERR_INTERNAL, "mmap of the zkey failed");
-    return NZCB_ERR_INTERNAL;
-  }
-  const int rc = nzcb_vk_from_zkey(static_cast<const uint8_t*>(m), (size_t)st.st_size, vk_out, err);
-  munmap(m, (size_t)st.st_size);
-  return rc;
+  return guarded(err, [&] {
+    if (!zkey_path || !vk_out) throw Error(NZCB_ERR_ARG, "null argument");
+    const MappedFile f(zkey_path, "the zkey", "zkey file is empty");
+    const Zkey z = parse_zkey(f.data, f.size);
+    vk_write(z, vk_out);
+  });
 }
 
 int nzcb_vk_to_json(const uint8_t* vk, char* out, size_t cap) {
@@ -539,21 +508,13 @@ int nzcb_vk_to_json(const uint8_t* vk, char* out, size_t cap) {
 
 int nzcb_verify(const uint8_t* vk, const uint8_t* proof, const uint8_t* pub, int n_public, int transcript_public,
                 int* valid, nzcb_err* err) {
-  try {
+  return guarded(err, [&] {
     if (!vk || !proof || !valid || n_public < 0 || (n_public && !pub)) throw Error(NZCB_ERR_ARG, "null argument");
     bool ok = true;
     const Vk v = vk_read(vk, &ok);
     if (!ok) throw Error(NZCB_ERR_FORMAT, "invalid verification key");
     *valid = plonk_verify(v, proof, pub, n_public, transcript_public != 0) ? 1 : 0;
-    if (err) err->code = 0;
-    return 0;
-  } catch (const Error& e) {
-    set_err(err, e.code, e.what());
-    return e.code;
-  } catch (const std::exception& e) {
-    set_err(err, NZCB_ERR_INTERNAL, e.what());
-    return NZCB_ERR_INTERNAL;
-  }
+  });
 }
 
 int nzcb_proof_to_calldata(const uint8_t* proof, const uint8_t* pub, int n_public, char* out, size_t cap) {

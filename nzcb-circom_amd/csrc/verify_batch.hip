@@ -21,7 +21,7 @@
 #include <cstring>
 #include <vector>
 
-#include "common.h"
+#include "devcall.h"
 #include "keccak.h"
 #include "msm.h"
 #include "transcript.h"
@@ -52,35 +52,6 @@ __global__ __launch_bounds__(kTermBlock) void k_g1_group_sum(const G1xyzz* __res
   const uint32_t lo = g ? group_end[g - 1] : 0u;
   g1_group_sum(terms, lo, group_end[g], out + size_t(16) * g);
 }
-
-// the calling thread's device for the duration of a call
-struct DeviceScope {
-  int prev = -1;
-  explicit DeviceScope(int device) {
-    NZ_HIP(hipGetDevice(&prev));
-    NZ_HIP(hipSetDevice(device));
-  }
-  ~DeviceScope() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
-
-struct CallStream {
-  hipStream_t st = nullptr;
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  void* buf = nullptr;
-  CallStream() {
-    NZ_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    for (auto& e : ev) NZ_HIP(hipEventCreate(&e));
-  }
-  ~CallStream() {
-    if (st) (void)hipStreamSynchronize(st);
-    if (buf) (void)hipFree(buf);
-    for (auto& e : ev)
-      if (e) (void)hipEventDestroy(e);
-    if (st) (void)hipStreamDestroy(st);
-  }
-};
 
 // phases of the calling thread's last batch (nzcb_debug_verify_batch_timings)
 thread_local double g_times[6] = {0, 0, 0, 0, 0, 0};
@@ -117,39 +88,31 @@ void g1_lincomb_device(int device, const uint8_t* points, const uint8_t* scalars
   const size_t n = check_groups(group_end, groups);
   g_times[2] = g_times[3] = 0;
   if (!groups) return;
-  int ndev = 0;
-  NZ_HIP(hipGetDeviceCount(&ndev));
-  if (device < 0 || device >= ndev) throw Error(NZCB_ERR_ARG, "no such device");
-  DeviceScope scope(device);
-  CallStream cs;
-  auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
-  const size_t o_pts = 0, o_sc = o_pts + up(64 * n), o_ge = o_sc + up(32 * n), o_terms = o_ge + up(4 * groups),
-               o_out = o_terms + up(sizeof(G1xyzz) * n), total = o_out + up(64 * groups);
-  NZ_HIP(hipMalloc(&cs.buf, total));
-  char* d = static_cast<char*>(cs.buf);
+  CallScope cs(device, nullptr, 3);
+  BlockLayout lay;
+  const size_t o_pts = lay.take(64 * n), o_sc = lay.take(32 * n), o_ge = lay.take(4 * groups),
+               o_terms = lay.take(sizeof(G1xyzz) * n), o_out = lay.take(64 * groups);
+  char* d = cs.alloc<char>(lay.total);
   if (n) {
     NZ_HIP(hipMemcpyAsync(d + o_pts, points, 64 * n, hipMemcpyHostToDevice, cs.st));
     NZ_HIP(hipMemcpyAsync(d + o_sc, scalars, 32 * n, hipMemcpyHostToDevice, cs.st));
   }
   NZ_HIP(hipMemcpyAsync(d + o_ge, group_end, 4 * groups, hipMemcpyHostToDevice, cs.st));
-  NZ_HIP(hipEventRecord(cs.ev[0], cs.st));
+  cs.record(0);
   if (n)
     k_g1_term_mul<<<grid_for(n, kTermBlock, 1u << 20), kTermBlock, 0, cs.st>>>(
         reinterpret_cast<const uint32_t*>(d + o_pts), reinterpret_cast<const uint32_t*>(d + o_sc),
         reinterpret_cast<G1xyzz*>(d + o_terms), (uint32_t)n);
-  NZ_HIP(hipEventRecord(cs.ev[1], cs.st));
+  cs.record(1);
   k_g1_group_sum<<<grid_for(groups, kTermBlock, 1u << 20), kTermBlock, 0, cs.st>>>(
       reinterpret_cast<const G1xyzz*>(d + o_terms), reinterpret_cast<const uint32_t*>(d + o_ge),
       reinterpret_cast<uint32_t*>(d + o_out), (uint32_t)groups);
-  NZ_HIP(hipEventRecord(cs.ev[2], cs.st));
+  cs.record(2);
   NZ_HIP(hipGetLastError());
   NZ_HIP(hipMemcpyAsync(out, d + o_out, 64 * groups, hipMemcpyDeviceToHost, cs.st));
   NZ_HIP(hipStreamSynchronize(cs.st));
-  float ms = 0;
-  NZ_HIP(hipEventElapsedTime(&ms, cs.ev[0], cs.ev[1]));
-  g_times[2] = ms;
-  NZ_HIP(hipEventElapsedTime(&ms, cs.ev[1], cs.ev[2]));
-  g_times[3] = ms;
+  g_times[2] = cs.elapsed(0, 1);
+  g_times[3] = cs.elapsed(1, 2);
 }
 
 void g1_lincomb(int device, const uint8_t* points, const uint8_t* scalars, const uint32_t* group_end, size_t groups,
@@ -295,21 +258,6 @@ void verify_batch(const uint8_t* vkb, const uint8_t* proofs, const uint8_t* pubs
   g_times[4] = ms_since(t0);
   g_times[5] = bs.checks;
   if (pairing_checks) *pairing_checks = bs.checks;
-}
-
-template <class F>
-int guarded(nzcb_err* err, F&& f) {
-  try {
-    f();
-    if (err) err->code = 0;
-    return 0;
-  } catch (const Error& e) {
-    set_err(err, e.code, e.what());
-    return e.code;
-  } catch (const std::exception& e) {
-    set_err(err, NZCB_ERR_INTERNAL, e.what());
-    return NZCB_ERR_INTERNAL;
-  }
 }
 
 }  // namespace

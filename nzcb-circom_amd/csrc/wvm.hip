@@ -1054,21 +1054,11 @@ struct nzcb_wprog {
 extern "C" {
 
 nzcb_wprog* nzcb_wprog_create(const uint8_t* prog, size_t len, int device, nzcb_err* err) {
-  try {
-    auto h = new nzcb_wprog();
-    try {
-      h->p = wvm::load(prog, len, device);
-    } catch (...) {
-      delete h;
-      throw;
-    }
+  return guarded_new<nzcb_wprog>(err, [&] {
+    auto h = std::make_unique<nzcb_wprog>();
+    h->p = wvm::load(prog, len, device);
     return h;
-  } catch (const Error& e) {
-    set_err(err, e.code, e.what());
-  } catch (const std::exception& e) {
-    set_err(err, NZCB_ERR_INTERNAL, e.what());
-  }
-  return nullptr;
+  });
 }
 
 void nzcb_wprog_destroy(nzcb_wprog* h) {
@@ -1092,24 +1082,17 @@ int nzcb_wprog_info(const nzcb_wprog* h, uint32_t info[5]) {
 
 int nzcb_wprog_run_dev(nzcb_wprog* h, const void* dev_inputs, int count, void* dev_witness, size_t witness_stride,
                        int32_t* status_out, void* stream, nzcb_err* err) {
-  try {
+  return guarded(err, [&] {
     if (!h) throw Error(NZCB_ERR_ARG, "witness program: null handle");
     wvm::run(h->p, dev_inputs, count, dev_witness, witness_stride, status_out, (hipStream_t)stream);
-    return NZCB_OK;
-  } catch (const Error& e) {
-    set_err(err, e.code, e.what());
-    return e.code;
-  } catch (const std::exception& e) {
-    set_err(err, NZCB_ERR_INTERNAL, e.what());
-    return NZCB_ERR_INTERNAL;
-  }
+  });
 }
 
 int nzcb_wprog_run(nzcb_wprog* h, const uint8_t* inputs, int count, uint8_t* witness_out, int32_t* status_out,
                    nzcb_err* err) {
-  try {
+  return guarded(err, [&] {
     if (!h) throw Error(NZCB_ERR_ARG, "witness program: null handle");
-    if (count <= 0) return NZCB_OK;
+    if (count <= 0) return;
     if (!inputs || !witness_out || !status_out) throw Error(NZCB_ERR_ARG, "witness program: null buffer");
     NZ_HIP(hipSetDevice(h->p->device));
     const size_t nin = (size_t)(h->p->n_pub + h->p->n_prv) * 32 * count;
@@ -1118,14 +1101,7 @@ int nzcb_wprog_run(nzcb_wprog* h, const uint8_t* inputs, int count, uint8_t* wit
     if (nin) NZ_HIP(hipMemcpy(din.p, inputs, nin, hipMemcpyHostToDevice));
     wvm::run(h->p, din.p, count, dw.p, nw, status_out, nullptr);
     NZ_HIP(hipMemcpy(witness_out, dw.p, nw * count, hipMemcpyDeviceToHost));
-    return NZCB_OK;
-  } catch (const Error& e) {
-    set_err(err, e.code, e.what());
-    return e.code;
-  } catch (const std::exception& e) {
-    set_err(err, NZCB_ERR_INTERNAL, e.what());
-    return NZCB_ERR_INTERNAL;
-  }
+  });
 }
 
 // circom .sym text: "label,wire,component,name" per line; wire < 0 = optimized out
@@ -1152,7 +1128,7 @@ static void parse_sym(const char* text, size_t len,
 
 int nzcb_wprog_remap(const uint8_t* prog, size_t len, const char* own_sym, size_t own_len, const char* target_sym,
                      size_t target_len, uint8_t** out, size_t* out_len, uint32_t* unmatched, nzcb_err* err) {
-  try {
+  return guarded(err, [&] {
     if (!prog || !own_sym || !target_sym || !out || !out_len) throw Error(NZCB_ERR_ARG, "null argument");
     if (unmatched) *unmatched = 0;
     if (len < 40 || std::memcmp(prog, "nzwp", 4) != 0) throw Error(NZCB_ERR_FORMAT, "witness program: bad magic");
@@ -1209,14 +1185,7 @@ int nzcb_wprog_remap(const uint8_t* prog, size_t len, const char* own_sym, size_
     std::memcpy(buf + len + 8, map.data(), (size_t)T * 4);
     *out = buf;
     *out_len = total;
-    return NZCB_OK;
-  } catch (const Error& e) {
-    set_err(err, e.code, e.what());
-    return e.code;
-  } catch (const std::exception& e) {
-    set_err(err, NZCB_ERR_INTERNAL, e.what());
-    return NZCB_ERR_INTERNAL;
-  }
+  });
 }
 
 }  // extern "C"
