@@ -122,6 +122,15 @@ int nzcb_engine_msm_fixed_dev(nzcb_engine* e, const void* bases, size_t n_table,
 int nzcb_engine_msm_table_dev(nzcb_engine* e, const void* bases, size_t n_table, const void* scalars, size_t n,
                               int scalars_mont, int window, int sparse, int fold, uint8_t* out_affine,
                               nzcb_err* err);
+/* nzcb_engine_msm_table_dev's dense schedule, and the segment plan it accumulated by (msm.hip
+ * msm_seg_scatter_kernel; NZCB_ACC_SEGMENTS): info[0] = 1 if the MSM ran by segments (0: by
+ * chunks, nothing else is filled), info[1] = bucket keys, info[2] = segments, info[3] = the
+ * segment cap kSegMax. offsets: info[1] + 1 bucket offsets; seg: the segments' first entry, then
+ * their lengths, then their buckets, info[2] values each, in plan order. NZCB_ERR_ARG if
+ * offsets_cap < info[1] + 1 or seg_cap < 3 * info[2]. */
+int nzcb_debug_msm_plan(nzcb_engine* e, const void* bases, size_t n_table, const void* scalars, size_t n,
+                        int scalars_mont, int window, int fold, uint32_t* info, uint32_t* offsets, size_t offsets_cap,
+                        uint32_t* seg, size_t seg_cap, uint8_t* out_affine, nzcb_err* err);
 /* `sets` (1..3) MSMs of n scalars each (device pointers scalars[0..sets)) over ONE Lagrange-window
  * table of the first n_table bases in one schedule (msm.hip msm_enqueue_sets: the prover's A, B,
  * C commitments since round 6); sparse = 0 is the schedule the prover runs by default, sparse = 1

@@ -344,6 +344,38 @@ int nzcb_engine_msm_table_dev(nzcb_engine* e, const void* bases, size_t n_table,
   });
 }
 
+int nzcb_debug_msm_plan(nzcb_engine* e, const void* bases, size_t n_table, const void* scalars, size_t n,
+                        int scalars_mont, int window, int fold, uint32_t* info, uint32_t* offsets, size_t offsets_cap,
+                        uint32_t* seg, size_t seg_cap, uint8_t* out_affine, nzcb_err* err) {
+  return guarded(err, [&] {
+    Engine& g = e->eng;
+    NZ_HIP(hipSetDevice(g.device));
+    if (n > n_table) throw Error(NZCB_ERR_ARG, "msm larger than its base table");
+    if (window && (window < 16 || window > 20)) throw Error(NZCB_ERR_ARG, "msm table window: 16..20");
+    MsmBaseTable t;
+    t.build((const G1Affine*)bases, n_table, window ? window : fixed_base_window(), g.stream, fold != 0);
+    MsmScratch sc;
+    sc.init(n ? n : 1, true);
+    G1xyzz r = msm(sc, (const G1Affine*)bases, (const Fr*)scalars, n, scalars_mont != 0, g.stream, &t);
+    affine_out(r, out_affine);
+    std::vector<uint32_t> off, start, len, bucket;
+    info[0] = msm_debug_plan(sc, g.stream, off, start, len, bucket) ? 1u : 0u;
+    info[1] = info[2] = 0;
+    info[3] = kSegMax;
+    if (!info[0]) return;
+    info[1] = (uint32_t)(off.size() - 1);
+    info[2] = (uint32_t)start.size();
+    if (off.size() > offsets_cap || 3 * start.size() > seg_cap)
+      throw Error(NZCB_ERR_ARG, "msm plan: the output arrays are too small");
+    std::memcpy(offsets, off.data(), off.size() * 4);
+    if (!start.empty()) {
+      std::memcpy(seg, start.data(), start.size() * 4);
+      std::memcpy(seg + start.size(), len.data(), start.size() * 4);
+      std::memcpy(seg + 2 * start.size(), bucket.data(), start.size() * 4);
+    }
+  });
+}
+
 int nzcb_engine_msm_sets_dev(nzcb_engine* e, const void* bases, size_t n_table, const void* const* scalars, int sets,
                              size_t n, int scalars_mont, int sparse, uint8_t* out_affine, nzcb_err* err) {
   return guarded(err, [&] {

@@ -5,6 +5,7 @@
 #include "common.h"
 #include "ec.h"
 #include "f29.h"
+#include "msm_seg.h"
 
 namespace nzcb {
 
@@ -35,6 +36,9 @@ int lagrange_window();
 // with NZCB_SPARSE=1; off by default: on nzcp_live's A, B, C it cost 0.8-1.3 % of proofs/s
 // against the dense schedule (profiles/r6_sets_ab.txt) for no single-proof latency gain
 bool lagrange_sparse();
+// Dense single-set tables accumulate whole-bucket segments, one per lane, in length order
+// (msm_accumulate29_seg_kernel) unless NZCB_ACC_SEGMENTS=0 keeps the 48-entry chunks.
+bool acc_segments();
 
 struct MsmScratch {
   size_t max_points = 0;
@@ -56,6 +60,13 @@ struct MsmScratch {
   DevBuf<uint32_t> large;     // [count, bucket ids...] of buckets with long carry runs
   DevBuf<uint32_t> large_off;  // fixed base: piece offsets of the listed buckets (msm_large_scan_kernel)
   DevBuf<Xyzz29> large_part;   // fixed base: one partial sum per piece
+  // dense single-set tables, NZCB_ACC_SEGMENTS=1 (msm.hip msm_seg_*_kernel): the buckets cut into
+  // segments of at most kSegMax entries, longest first, stable by bucket within a length.
+  // seg_dst: the bucket a whole bucket's sum goes to, or 1 << 31 | the bucket's first whole
+  // segment (its pieces' carry slot). seg_cnt: (length class, tile) counters, class totals.
+  // seg_meta: [segments, buckets cut into pieces]. seg_mk / seg_mfs / seg_mnp: those buckets,
+  // their first whole segment, and whole segments | rest << 31.
+  DevBuf<uint32_t> seg_start, seg_len, seg_bucket, seg_dst, seg_cnt, seg_meta, seg_mk, seg_mfs, seg_mnp;
   // fixed-base window sum (msm.hip msm_tile29_kernel): row / column partials per tile, lines
   DevBuf<Xyzz29> rowp29, colp29, lines29;
   DevBuf<G1xyzz> seg_tot;     // generic: per (bucket set, segment): sum_j (j+1) * bucket_j
@@ -68,6 +79,7 @@ struct MsmScratch {
   // shape of the MSM in flight (set by msm_enqueue, used by msm_finish)
   int cur_c = 0, cur_nsets = 0, cur_nbits = 0, cur_seglen = 0;
   bool cur_fixed = false, cur_sparse = false;
+  bool cur_seg = false;  // the segment plan was used (msm_debug_plan)
   int cur_a = 0, cur_hb = 0;  // fixed base: column / row bits of the window sum
   int cur_msets = 1;          // fixed base: MSMs in the schedule (msm_enqueue_sets)
   size_t cur_n = 0;
@@ -111,6 +123,11 @@ inline G1xyzz msm(MsmScratch& sc, const G1Affine* bases, const Fr* scalars, size
   msm_enqueue(sc, bases, scalars, n, mont, st, table);
   return msm_finish(sc, st);
 }
+
+// The segment plan of the last fixed-base MSM on `sc` (tests): bucket offsets (nkeys + 1) and
+// the segments' first entry, length and bucket in plan order. False if that MSM ran in chunks.
+bool msm_debug_plan(MsmScratch& sc, hipStream_t st, std::vector<uint32_t>& offsets, std::vector<uint32_t>& start,
+                    std::vector<uint32_t>& len, std::vector<uint32_t>& bucket);
 
 // Host helpers.
 G1Affine xyzz_to_affine(const G1xyzz& p);

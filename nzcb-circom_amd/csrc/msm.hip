@@ -154,6 +154,14 @@ bool lagrange_sparse() {
   return v;
 }
 
+bool acc_segments() {
+  static const bool v = [] {
+    const char* e = std::getenv("NZCB_ACC_SEGMENTS");
+    return e ? std::atoi(e) != 0 : true;
+  }();
+  return v;
+}
+
 int msm_window_bits(size_t n) {
   if (n >= (size_t(1) << 18)) return 16;
   int lg = ilog2(n ? n : 1);
@@ -746,6 +754,49 @@ __device__ __forceinline__ G1xyzz load_point(const Xyzz29& a) {
   return r;
 }
 
+// One table entry into a lane's running sum (inf: no sum yet): madd-2008-s, the only inlined
+// addition of the accumulation kernels' loops. ent's top bit negates the point.
+__device__ __forceinline__ void acc_entry29(Xyzz29& acc, bool& inf, const G1Affine& P, uint32_t ent) {
+  if (P.is_inf()) return;
+  const F29 x = split29(P.x);
+  F29 y = split29(P.y);
+  if (ent >> 31) y = neg29_nn(y);  // 2p - y, limbs < 2^30: only S2's product reads it
+  if (inf) {
+    norm29(y);
+    acc.X = x;
+    acc.Y = y;
+    acc.ZZ = f29_const(Fq29::ONE);
+    acc.ZZZ = f29_const(Fq29::ONE);
+    inf = false;
+  } else {
+    // madd-2008-s (XYZZ + affine): 8 products + 2 squares, in pairs
+    F29 U2, S2, PP, RR;
+    mul29x2<Fq29>(x, acc.ZZ, y, acc.ZZZ, U2, S2);
+    const F29 Pd = sub29(U2, acc.X, Fq29::K8);   // < 10p
+    const F29 R = sub29(S2, acc.Y, Fq29::K4);    // < 6p
+    sqr29x2(Pd, R, PP, RR);
+    if (is0p29_fast(PP)) {  // same abscissa: doubling (equal points) or infinity (opposite)
+      if (is0p29(RR)) {
+        norm29(y);
+        mdbl29_rare(x, y, &acc);
+      } else {
+        inf = true;
+      }
+    } else {
+      F29 PPP, Q, ZZ3, ZZZ3;
+      mul29x2<Fq29>(Pd, PP, acc.X, PP, PPP, Q);
+      const F29 X3 = sub2x29(RR, PPP, Q);  // RR + 6p - PPP - 2Q < 8p
+      mul29x2<Fq29>(acc.ZZ, PP, acc.ZZZ, PPP, ZZ3, ZZZ3);
+      // Y3 = R (Q - X3) + (4p - Y1) PPP, one reduction: (6p 12p + 4p 2p) / 2^261 + p < 2p;
+      // Q - X3 + 10p (limbs < 2^30.6) and 4p - Y1 (limbs < 2^30) stay unnormalized
+      acc.Y = mul2sum29(R, sub29_nn(Q, X3, Fq29W::K10), neg4p29_nn(acc.Y), PPP);
+      acc.ZZ = ZZ3;
+      acc.ZZZ = ZZZ3;
+      acc.X = X3;
+    }
+  }
+}
+
 // kLdsIdx (chunk <= kChunk): the workgroup's kMsmThreads x chunk slice of `sorted` is
 // staged into LDS by coalesced loads before the additions. Read from HBM one index per
 // addition, each lane's chunk 192 B from its neighbour's, the index lines were evicted
@@ -808,45 +859,7 @@ msm_accumulate29_kernel(uint32_t chunk, const G1Affine* __restrict__ bases, cons
     uint32_t ent_nn = 0;
     if (pos + 1 < e) Pn = bases[ent_n & 0x7fffffffu];
     if (pos + 2 < e) ent_nn = index_at(pos + 2);
-    if (!P.is_inf()) {
-      const F29 x = split29(P.x);
-      F29 y = split29(P.y);
-      if (ent >> 31) y = neg29_nn(y);  // 2p - y, limbs < 2^30: only S2's product reads it
-      if (inf) {
-        norm29(y);
-        acc.X = x;
-        acc.Y = y;
-        acc.ZZ = f29_const(Fq29::ONE);
-        acc.ZZZ = f29_const(Fq29::ONE);
-        inf = false;
-      } else {
-        // madd-2008-s (XYZZ + affine): 8 products + 2 squares, in pairs
-        F29 U2, S2, PP, RR;
-        mul29x2<Fq29>(x, acc.ZZ, y, acc.ZZZ, U2, S2);
-        const F29 Pd = sub29(U2, acc.X, Fq29::K8);   // < 10p
-        const F29 R = sub29(S2, acc.Y, Fq29::K4);    // < 6p
-        sqr29x2(Pd, R, PP, RR);
-        if (is0p29_fast(PP)) {  // same abscissa: doubling (equal points) or infinity (opposite)
-          if (is0p29(RR)) {
-            norm29(y);
-            mdbl29_rare(x, y, &acc);
-          } else {
-            inf = true;
-          }
-        } else {
-          F29 PPP, Q, ZZ3, ZZZ3;
-          mul29x2<Fq29>(Pd, PP, acc.X, PP, PPP, Q);
-          const F29 X3 = sub2x29(RR, PPP, Q);  // RR + 6p - PPP - 2Q < 8p
-          mul29x2<Fq29>(acc.ZZ, PP, acc.ZZZ, PPP, ZZ3, ZZZ3);
-          // Y3 = R (Q - X3) + (4p - Y1) PPP, one reduction: (6p 12p + 4p 2p) / 2^261 + p < 2p;
-          // Q - X3 + 10p (limbs < 2^30.6) and 4p - Y1 (limbs < 2^30) stay unnormalized
-          acc.Y = mul2sum29(R, sub29_nn(Q, X3, Fq29W::K10), neg4p29_nn(acc.Y), PPP);
-          acc.ZZ = ZZ3;
-          acc.ZZZ = ZZZ3;
-          acc.X = X3;
-        }
-      }
-    }
+    acc_entry29(acc, inf, P, ent);
     pos++;
     if (pos == kend || pos == e) {
       const bool starts = kstart >= s;
@@ -869,6 +882,182 @@ msm_accumulate29_kernel(uint32_t chunk, const G1Affine* __restrict__ bases, cons
     }
     ent = ent_n;
     ent_n = ent_nn;
+    P = Pn;
+  }
+}
+
+// ---- dense single-set tables: whole-bucket segments, one per lane (NZCB_ACC_SEGMENTS) ----
+// A lane that owns a whole bucket starts one sum, adds to it and stores it once: no run-start
+// and run-end blocks inside the loop, no carry and no addition in the finalize. Load balance
+// must not depend on the digits (the reason for fixed chunks), so the buckets are cut into
+// segments of at most kSegMax entries and the segments ordered by length, longest first: the
+// 64 lanes of a wave then run the same number of iterations but for the waves that straddle
+// a length-class edge, and the waves launch in longest-first order.
+// The plan is a stable counting sort on the segment length over tiles of kSegTile buckets,
+// one tile per wave, from the bucket offsets msm_lo_scan_kernel wrote:
+//   msm_seg_hist_kernel     per (length class, tile): segments of that length in the tile
+//   msm_bin_rowscan_kernel  per class: exclusive scan over the tiles, class totals
+//   msm_seg_scatter_kernel  the tile's segments to their places, in bucket order within a
+//                           class (ranks by wave ballots: no atomics decide a place, so two
+//                           runs give the same plan), and the list of buckets cut into pieces
+// A bucket of len entries makes len / kSegMax whole segments (class kSegMax, consecutive in the
+// plan, at fs..) and the rest (class len % kSegMax). A bucket in one segment stores to its
+// bucket; the pieces of one cut into several are carries: whole segment fs + u to
+// carry_cont[fs + u], the rest to carry_own[fs].
+struct SegPlan {
+  uint32_t *start, *len, *bucket, *dst;  // per segment, in plan order
+  uint32_t *mk, *mfs, *mnp;              // per bucket cut into pieces: bucket, fs, whole | rest << 31
+  uint32_t* meta;                        // [segments, buckets cut into pieces]
+};
+
+static constexpr int kSegThreads = 256;
+static constexpr uint32_t kSegWaves = kSegThreads / 64;
+
+__global__ void __launch_bounds__(kSegThreads)
+msm_seg_hist_kernel(const uint32_t* __restrict__ offsets, uint32_t nkeys, uint32_t ntiles,
+                    uint32_t* __restrict__ cnt, uint32_t* __restrict__ meta) {
+  __shared__ uint32_t h[kSegWaves][kSegMax + 1];
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const uint32_t tile = blockIdx.x * kSegWaves + wave;
+  for (uint32_t i = threadIdx.x; i < kSegWaves * (kSegMax + 1); i += kSegThreads) (&h[0][0])[i] = 0;
+  if (blockIdx.x == 0 && threadIdx.x == 0) meta[1] = 0;  // the scatter counts the cut buckets
+  __syncthreads();
+  if (tile < ntiles) {
+    for (uint32_t it = 0; it < kSegTile / 64; it++) {
+      const uint32_t k = tile * kSegTile + it * 64 + lane;
+      if (k >= nkeys) break;
+      const uint32_t len = offsets[k + 1] - offsets[k];
+      const uint32_t whole = len / kSegMax, rest = len % kSegMax;
+      if (whole) atomicAdd(&h[wave][kSegMax], whole);
+      if (rest) atomicAdd(&h[wave][rest], 1u);
+    }
+  }
+  __syncthreads();
+  if (tile < ntiles)  // row kSegMax - L: the longest class first
+    for (uint32_t L = 1 + lane; L <= kSegMax; L += 64) cnt[(size_t)(kSegMax - L) * ntiles + tile] = h[wave][L];
+}
+
+__global__ void __launch_bounds__(kSegThreads)
+msm_seg_scatter_kernel(const uint32_t* __restrict__ offsets, uint32_t nkeys, uint32_t ntiles,
+                       const uint32_t* __restrict__ cnt, SegPlan pl) {
+  __shared__ uint32_t cb[256], wsum[4];
+  __shared__ uint32_t base_s[kSegWaves][kSegMax + 1];
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const uint32_t tile = blockIdx.x * kSegWaves + wave;
+  uint32_t total;
+  const uint32_t* tail = cnt + (size_t)kSegMax * ntiles;  // class totals (msm_bin_rowscan_kernel)
+  cb[threadIdx.x] = scan256_excl(threadIdx.x < kSegMax ? tail[threadIdx.x] : 0u, wsum, total);
+  if (blockIdx.x == 0 && threadIdx.x == 0) pl.meta[0] = total;
+  __syncthreads();
+  volatile uint32_t* base = base_s[wave];  // the wave's next place per class
+  if (tile < ntiles)
+    for (uint32_t L = 1 + lane; L <= kSegMax; L += 64)
+      base[L] = cb[kSegMax - L] + cnt[(size_t)(kSegMax - L) * ntiles + tile];
+  __syncthreads();
+  if (tile >= ntiles) return;
+  for (uint32_t it = 0; it < kSegTile / 64; it++) {
+    const uint32_t k0 = tile * kSegTile + it * 64;
+    if (k0 >= nkeys) break;  // wave-uniform
+    const uint32_t k = k0 + lane;
+    const uint32_t s = k < nkeys ? offsets[k] : 0u;
+    const uint32_t len = k < nkeys ? offsets[k + 1] - s : 0u;
+    const uint32_t whole = len / kSegMax, rest = len % kSegMax;
+    const bool cut = whole + (rest ? 1u : 0u) > 1;
+    // whole segments: the lanes' counts scanned, places in lane (= bucket) order
+    const uint32_t incl = wave_incl_scan(whole);
+    const uint32_t wtot = __shfl(incl, 63, 64);
+    const uint32_t fs = base[kSegMax] + incl - whole;
+    if (lane == 0 && wtot) base[kSegMax] = fs + wtot;  // after every lane's read above (one instruction)
+    const uint32_t dst = cut ? 0x80000000u | fs : k;
+    for (uint32_t j = 0; j < whole; j++) {
+      pl.start[fs + j] = s + j * kSegMax;
+      pl.len[fs + j] = kSegMax;
+      pl.bucket[fs + j] = k;
+      pl.dst[fs + j] = dst;
+    }
+    // the rest: rank among the wave's lanes with the same length
+    uint64_t same = __ballot(rest != 0);
+#pragma unroll
+    for (uint32_t b = 0; (1u << b) < kSegMax; b++) {
+      const uint64_t bb = __ballot((rest >> b) & 1u);
+      same &= ((rest >> b) & 1u) ? bb : ~bb;
+    }
+    if (rest) {
+      const uint32_t rank = __popcll(same & ((1ull << lane) - 1ull));
+      const uint32_t at = base[rest] + rank;
+      if (rank == 0) base[rest] = at + __popcll(same);
+      pl.start[at] = s + whole * kSegMax;
+      pl.len[at] = rest;
+      pl.bucket[at] = k;
+      pl.dst[at] = dst;
+    }
+    if (cut) {
+      const uint32_t m = atomicAdd(&pl.meta[1], 1u);  // the list's order decides no result
+      pl.mk[m] = k;
+      pl.mfs[m] = fs;
+      pl.mnp[m] = whole | (rest ? 0x80000000u : 0u);
+    }
+  }
+}
+
+// Lane i adds segment i: one sum started at its first entry, the madd-2008-s body for the
+// rest, one store when the lane's last entry is in. Each lane loops over its own length; the
+// wave runs for its longest, lane 0's, and as the plan's lengths do not increase the others
+// differ from it only where a wave straddles a length-class edge: those lanes (and the last
+// wave's lanes past the plan) sit masked for the difference, with no per-lane branch besides
+// the loop's own exit.
+// Indices: per-lane 16-byte loads of four entries from `sorted` (dword-aligned: a segment
+// starts anywhere), one load per four iterations, issued a whole iteration before its first
+// entry becomes `nxt`; at most six index registers are live. A 64-byte index line then serves
+// 16 iterations of one lane in 4 or 5 loads instead of 16 (the re-fetch of evicted index lines
+// that made the chunked kernel stage its indices in LDS), and the kernel needs no LDS: the
+// 49 KB stage is a workgroup-wide transpose of a contiguous slice of the stream, which
+// segments that start anywhere in it do not have.
+// Registers (168 VGPRs, no scratch) hang on the form of the store: with the sum stored after
+// the loop, or zeroed in place instead of through the copy `out`, the allocator spilled 34 to
+// 117 VGPRs, the prefetched point among them.
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef u32x4 u32x4_a4 __attribute__((aligned(4)));
+
+__global__ void __launch_bounds__(kMsmThreads) __attribute__((amdgpu_waves_per_eu(3, 8)))
+msm_accumulate29_seg_kernel(const G1Affine* __restrict__ bases, const uint32_t* __restrict__ sorted,
+                            const uint32_t* __restrict__ seg_start, const uint32_t* __restrict__ seg_len,
+                            const uint32_t* __restrict__ seg_dst, const uint32_t* __restrict__ meta,
+                            Xyzz29* __restrict__ buckets, Xyzz29* __restrict__ carry_own,
+                            Xyzz29* __restrict__ carry_cont) {
+  const uint32_t i = blockIdx.x * kMsmThreads + threadIdx.x;  // < 2^32 (seg_bound)
+  const uint32_t nseg = meta[0];
+  if (i >= nseg) return;  // past the plan: the grid covers seg_bound
+  const uint32_t s = seg_start[i], len = seg_len[i];
+  // ent, nxt: entries j, j + 1; g: j + 2 and on. A load reads at most sorted[s + len + 2]
+  // (MsmScratch::init pads `sorted`)
+  u32x4 g = *(const u32x4_a4*)(sorted + s);
+  uint32_t ent = g.x, nxt = g.y;
+  g.x = g.z;
+  g.y = g.w;
+  G1Affine P = bases[ent & 0x7fffffffu];
+  Xyzz29 acc;
+  bool inf = true;
+  const uint32_t dst = seg_dst[i];
+  Xyzz29* o = !(dst >> 31) ? buckets + dst : len == kSegMax ? carry_cont + i : carry_own + (dst & 0x7fffffffu);
+  for (uint32_t j = 0; j < len;) {
+    G1Affine Pn;
+    if (j + 1 < len) Pn = bases[nxt & 0x7fffffffu];  // the next entry's point, behind this addition
+    acc_entry29(acc, inf, P, ent);
+    j++;
+    if (j == len) {  // the segment's sum: the only store
+      Xyzz29 out = acc;
+      if (inf)
+#pragma unroll
+        for (int u = 0; u < 9; u++) out.ZZ.v[u] = 0;
+      *o = out;
+    }
+    ent = nxt;
+    nxt = g.x;
+    g.x = g.y;
+    g.y = g.z;
+    g.z = g.w;
+    if ((j & 3u) == 2u && j + 2 < len) g = *(const u32x4_a4*)(sorted + s + j + 2);
     P = Pn;
   }
 }
@@ -914,45 +1103,77 @@ msm_bucket_finalize_kernel(uint32_t chunk, const uint32_t* __restrict__ offsets,
 // partial sum in place (out29) and their carry range in LDS (12 B each: the kernel keeps
 // the accumulation's LDS free), and the first waves finish them after a barrier (usually
 // one wave, one more round). Isolated 2^21 MSM: 0.149 -> 0.12 ms, VALU -34 %.
+//
+// A bucket's carries, for this kernel and msm_large_*: `span` of them, carry u at
+// carry_cont[c0 + u] but for u == own, which is carry_own[c0]. Chunks (kSeg = false): c0 the
+// bucket's first chunk, own = 0. Segments (kSeg = true): the kernels run over the plan's list of
+// buckets cut into pieces and the large list holds positions in that list; c0 = the bucket's
+// first whole segment, own = its whole segments (= span if it has no rest).
+struct CarryRun {
+  uint32_t k, c0, span, own;
+};
+template <bool kSeg>
+__device__ __forceinline__ CarryRun carry_run(uint32_t chunk, const uint32_t* __restrict__ offsets,
+                                              const SegPlan& pl, uint32_t id) {
+  CarryRun r;
+  if (kSeg) {
+    const uint32_t np = pl.mnp[id];
+    r.k = pl.mk[id];
+    r.c0 = pl.mfs[id];
+    r.own = np & 0x7fffffffu;
+    r.span = r.own + (np >> 31);
+  } else {
+    r.k = id;
+    r.c0 = offsets[id] / chunk;
+    r.span = (offsets[id + 1] - 1) / chunk - r.c0 + 1;
+    r.own = 0;
+  }
+  return r;
+}
+__device__ __forceinline__ const Xyzz29& carry_at(const Xyzz29* __restrict__ carry_own,
+                                                  const Xyzz29* __restrict__ carry_cont, const CarryRun& r,
+                                                  uint32_t u) {
+  return u == r.own ? carry_own[r.c0] : carry_cont[r.c0 + u];
+}
+
+template <bool kSeg>
 __global__ void __launch_bounds__(kMsmThreads)
 msm_finalize29_kernel(uint32_t chunk, const uint32_t* __restrict__ offsets, uint32_t nkeys, uint32_t span,
                       const Xyzz29* __restrict__ carry_own, const Xyzz29* __restrict__ carry_cont,
-                      uint32_t* __restrict__ large, Xyzz29* __restrict__ out29) {
+                      uint32_t* __restrict__ large, Xyzz29* __restrict__ out29, SegPlan pl) {
   tail_prio();
-  __shared__ uint32_t pk[kMsmThreads], pu[kMsmThreads], pe[kMsmThreads];
+  __shared__ uint32_t pk[kMsmThreads], pc[kMsmThreads], pe[kMsmThreads], po[kMsmThreads];
   __shared__ uint32_t cnt;
   if (threadIdx.x == 0) cnt = 0;
-  if (!chunk) chunk = dyn_chunk(offsets[nkeys]);  // sparse tables
+  if (!kSeg && !chunk) chunk = dyn_chunk(offsets[nkeys]);  // sparse tables
   __syncthreads();
-  const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  uint32_t c0 = 0, c1 = 0;
+  const size_t id = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  CarryRun r{0, 0, 0, 0};
   bool mine = false;
-  if (k < nkeys) {
-    const uint32_t s = offsets[k], e = offsets[k + 1];
-    if (e != s) {
-      c0 = s / chunk;
-      c1 = (e - 1) / chunk;
-      if (c1 - c0 > span)  // long run (skewed digits): msm_large_*
-        large[1 + atomicAdd(&large[0], 1u)] = (uint32_t)k;
-      else
-        mine = c1 > c0;  // single-chunk buckets were stored by the accumulation
-    }
+  // single-chunk (single-segment) buckets were stored by the accumulation
+  if (id < (kSeg ? pl.meta[1] : nkeys) && (kSeg || offsets[id + 1] != offsets[id])) {
+    r = carry_run<kSeg>(chunk, offsets, pl, (uint32_t)id);
+    if (r.span - 1 > span)  // long run (skewed digits): msm_large_*
+      large[1 + atomicAdd(&large[0], 1u)] = (uint32_t)id;
+    else
+      mine = r.span > 1;
   }
   if (mine) {
-    out29[k] = add29(carry_own[c0], carry_cont[c0 + 1]);
-    if (c1 > c0 + 1) {
+    out29[r.k] = add29(carry_at(carry_own, carry_cont, r, 0), carry_at(carry_own, carry_cont, r, 1));
+    if (r.span > 2) {
       const uint32_t i = atomicAdd(&cnt, 1u);
-      pk[i] = (uint32_t)k;
-      pu[i] = c0 + 2;
-      pe[i] = c1;
+      pk[i] = r.k;
+      pc[i] = r.c0;
+      pe[i] = r.span;
+      po[i] = r.own;
     }
   }
   __syncthreads();  // (workgroup-scope fence: the parked sums are visible to the finishing lanes)
   if (threadIdx.x < cnt) {
-    const uint32_t kk = pk[threadIdx.x], u1 = pe[threadIdx.x];
-    Xyzz29 v = out29[kk];
-    for (uint32_t u = pu[threadIdx.x]; u <= u1; u++) v = add29(v, carry_cont[u]);
-    out29[kk] = v;
+    const CarryRun w{pk[threadIdx.x], pc[threadIdx.x], pe[threadIdx.x], po[threadIdx.x]};
+    Xyzz29 v = out29[w.k];
+    for (uint32_t u = 2; u < w.span; u++) v = add29(v, carry_at(carry_own, carry_cont, w, u));
+    out29[w.k] = v;
   }
 }
 
@@ -1058,27 +1279,22 @@ msm_bucket_large_kernel(uint32_t chunk, const uint32_t* __restrict__ offsets, co
 // one after another).
 static constexpr uint32_t kPieceCarries = (uint32_t)kSumThreads;
 
-__device__ __forceinline__ uint32_t carry_span(uint32_t chunk, const uint32_t* offsets, uint32_t k, uint32_t* c0) {
-  *c0 = offsets[k] / chunk;
-  return (offsets[k + 1] - 1) / chunk - *c0 + 1;
-}
-
 // off[i] = pieces of the listed buckets before i, off[count] = all (one workgroup).
 // chunk 0: the sparse schedule's device-derived chunk (dyn_chunk)
+template <bool kSeg>
 __global__ void __launch_bounds__(1024)
 msm_large_scan_kernel(uint32_t chunk, const uint32_t* __restrict__ offsets, uint32_t nkeys,
-                      const uint32_t* __restrict__ large, uint32_t* __restrict__ off) {
+                      const uint32_t* __restrict__ large, uint32_t* __restrict__ off, SegPlan pl) {
   tail_prio();
   __shared__ uint32_t sh[1024];
   const uint32_t count = large[0];
-  const uint32_t ch = chunk ? chunk : dyn_chunk(offsets[nkeys]);
+  const uint32_t ch = kSeg || chunk ? chunk : dyn_chunk(offsets[nkeys]);
   const uint32_t tid = threadIdx.x;
   const uint32_t per = (count + 1023u) / 1024u;
   const uint32_t i0 = tid * per < count ? tid * per : count;
   const uint32_t i1 = i0 + per < count ? i0 + per : count;
   auto pieces = [&](uint32_t i) {
-    uint32_t c0;
-    return (carry_span(ch, offsets, large[1 + i], &c0) + kPieceCarries - 1) / kPieceCarries;
+    return (carry_run<kSeg>(ch, offsets, pl, large[1 + i]).span + kPieceCarries - 1) / kPieceCarries;
   };
   uint32_t sum = 0;
   for (uint32_t i = i0; i < i1; i++) sum += pieces(i);
@@ -1124,29 +1340,29 @@ __device__ __forceinline__ Xyzz29 tree_sum29(Xyzz29 v, uint32_t cnt, Xyzz29* sh)
   return v;
 }
 
+template <bool kSeg>
 __global__ void __launch_bounds__(kSumThreads)
 msm_large_piece29_kernel(uint32_t chunk, const uint32_t* __restrict__ offsets, uint32_t nkeys,
                          const uint32_t* __restrict__ large, const uint32_t* __restrict__ off,
                          const Xyzz29* __restrict__ carry_own, const Xyzz29* __restrict__ carry_cont,
-                         Xyzz29* __restrict__ part) {
+                         Xyzz29* __restrict__ part, SegPlan pl) {
   tail_prio();
   __shared__ Xyzz29 sh[kSumThreads];
   const uint32_t count = large[0];
   const uint32_t total = off[count];
-  const uint32_t ch = chunk ? chunk : dyn_chunk(offsets[nkeys]);
+  const uint32_t ch = kSeg || chunk ? chunk : dyn_chunk(offsets[nkeys]);
   for (uint32_t item = blockIdx.x; item < total; item += gridDim.x) {
     uint32_t lo = 0, hi = count;  // largest i with off[i] <= item
     while (hi - lo > 1) {
       const uint32_t mid = (lo + hi) >> 1;
       if (off[mid] <= item) lo = mid; else hi = mid;
     }
-    uint32_t c0;
-    const uint32_t span = carry_span(ch, offsets, large[1 + lo], &c0);
+    const CarryRun r = carry_run<kSeg>(ch, offsets, pl, large[1 + lo]);
     const uint32_t first = (item - off[lo]) * kPieceCarries;
-    const uint32_t n = span - first < kPieceCarries ? span - first : kPieceCarries;
+    const uint32_t n = r.span - first < kPieceCarries ? r.span - first : kPieceCarries;
     const uint32_t u = first + threadIdx.x;
     Xyzz29 v;
-    if (threadIdx.x < n) v = u ? carry_cont[c0 + u] : carry_own[c0];
+    if (threadIdx.x < n) v = carry_at(carry_own, carry_cont, r, u);
     v = tree_sum29(v, n, sh);
     if (threadIdx.x == 0) part[item] = v;
     __syncthreads();  // sh is reused by the next item
@@ -1158,24 +1374,26 @@ msm_large_piece29_kernel(uint32_t chunk, const uint32_t* __restrict__ offsets, u
 // one-wave workgroups (64 threads, as until round 5): it finds nothing to do for random
 // scalars, and a 4-wave workgroup of 213 VGPRs waited longer for a free SIMD under the
 // other lanes' accumulations; the sparse tables' bucket 0 holds hundreds of pieces (256).
-template <int NT>
+template <int NT, bool kSeg = false>
 __global__ void __launch_bounds__(NT)
 msm_large_final29_kernel(const uint32_t* __restrict__ large, const uint32_t* __restrict__ off,
-                         const Xyzz29* __restrict__ part, Xyzz29* __restrict__ out29) {
+                         const Xyzz29* __restrict__ part, Xyzz29* __restrict__ out29,
+                         const uint32_t* __restrict__ seg_mk) {
   tail_prio();
   __shared__ Xyzz29 sh[NT];
   const uint32_t count = large[0];
   for (uint32_t i = blockIdx.x; i < count; i += gridDim.x) {
     const uint32_t p0 = off[i], np = off[i + 1] - p0;
+    const uint32_t k = kSeg ? seg_mk[large[1 + i]] : large[1 + i];  // segments: the list holds cut-bucket positions
     if (np == 1) {
-      if (threadIdx.x == 0) out29[large[1 + i]] = part[p0];
+      if (threadIdx.x == 0) out29[k] = part[p0];
       continue;
     }
     Xyzz29 v;
     if (threadIdx.x < np) v = part[p0 + threadIdx.x];
     for (uint32_t q = threadIdx.x + NT; q < np; q += NT) v = add29(v, part[p0 + q]);
     v = tree_sum29(v, np < NT ? np : NT, sh);
-    if (threadIdx.x == 0) out29[large[1 + i]] = v;
+    if (threadIdx.x == 0) out29[k] = v;
     __syncthreads();
   }
 }
@@ -1559,7 +1777,7 @@ void MsmScratch::init(size_t maxp, bool fixed_base, int lagrange_sets, bool gene
   // none of the generic schedule's sort, 8x32 bucket and segment arrays
   const size_t ge = generic ? max_entries : 1;
   offsets.alloc(max_keys + 1);
-  sorted.alloc(max_entries);
+  sorted.alloc(max_entries + 4);  // msm_accumulate29_seg_kernel reads four entries at a time: up to 3 past the last
   keys_in.alloc(ge);
   keys_out.alloc(max_entries);  // the fixed-base bucketing's low key parts
   vals_in.alloc(ge);
@@ -1569,7 +1787,9 @@ void MsmScratch::init(size_t maxp, bool fixed_base, int lagrange_sets, bool gene
   }
   sort_tmp.alloc(sort_tmp_bytes + 16);
   // accumulation threads: chunk_for's grid, or the sparse schedule's (dyn_threads_bound)
-  const size_t nthreads = std::max((max_entries + kChunk - 1) / kChunk, dyn_threads_bound(max_entries)) + 1;
+  // (or, per carry array, the whole segments of the segment plan)
+  const size_t nthreads = std::max({(max_entries + kChunk - 1) / kChunk, dyn_threads_bound(max_entries),
+                                    seg_whole_bound(max_entries)}) + 1;
   buckets.alloc(generic ? max_keys : 1);
   carry_own.alloc(generic ? nthreads : 1);
   carry_cont.alloc(generic ? nthreads : 1);
@@ -1578,7 +1798,8 @@ void MsmScratch::init(size_t maxp, bool fixed_base, int lagrange_sets, bool gene
     buckets29.alloc(max_keys);
     large_off.alloc(max_keys + 2);
     // pieces: sum over listed buckets of ceil(span / kPieceCarries) <= chunks / kPieceCarries + buckets
-    large_part.alloc(nthreads / kPieceCarries + max_keys + 1);
+    // (segments: carries <= seg_carry_bound, listed buckets <= seg_multi_bound <= max_keys)
+    large_part.alloc(std::max(nthreads, seg_carry_bound(max_entries, max_keys)) / kPieceCarries + max_keys + 1);
     carry_own29.alloc(nthreads);
     carry_cont29.alloc(nthreads);
     rowp29.alloc(max_tiles);
@@ -1587,6 +1808,18 @@ void MsmScratch::init(size_t maxp, bool fixed_base, int lagrange_sets, bool gene
     bin_counts.alloc((size_t)256 * ((maxp + kTileScalars - 1) / kTileScalars) * lagrange_sets + 256);  // + row totals
     vals_mid.alloc(max_entries);
     lo_seg.alloc(lo_items_bound(max_entries) * ((size_t)1 << BinKeys<19>::LO));  // the widest low index
+    if (acc_segments()) {
+      const size_t ns = seg_bound(max_entries, max_keys), nm = seg_multi_bound(max_entries, max_keys) + 1;
+      seg_start.alloc(ns);
+      seg_len.alloc(ns);
+      seg_bucket.alloc(ns);
+      seg_dst.alloc(ns);
+      seg_cnt.alloc(seg_counters(max_keys));
+      seg_meta.alloc(2);
+      seg_mk.alloc(nm);
+      seg_mfs.alloc(nm);
+      seg_mnp.alloc(nm);
+    }
   }
   seg_tot.alloc(max_seg && generic ? max_seg : 1);
   seg_run.alloc(max_seg && generic ? max_seg : 1);
@@ -1748,8 +1981,16 @@ static void msm_enqueue_impl(MsmScratch& sc, const G1Affine* bases, const Fr* co
     }
   }
 #endif
-  if (p.entries > sc.sorted.n || p.nkeys + 1 > sc.offsets.n)
+  if (p.entries + 4 > sc.sorted.n || p.nkeys + 1 > sc.offsets.n)
     throw Error(NZCB_ERR_ARG, "msm scratch was not sized for this schedule");
+  // dense single-set tables: whole-bucket segments (msm_accumulate29_seg_kernel)
+  const bool seg = table && !table->sparse && msets == 1 && acc_segments();
+  if (seg && (seg_bound(p.entries, p.nkeys) > sc.seg_start.n || seg_counters(p.nkeys) > sc.seg_cnt.n ||
+              seg_multi_bound(p.entries, p.nkeys) + 1 > sc.seg_mk.n ||
+              seg_whole_bound(p.entries) + 1 > sc.carry_cont29.n ||
+              seg_carry_bound(p.entries, p.nkeys) / kPieceCarries + seg_multi_bound(p.entries, p.nkeys) + 1 >
+                  sc.large_part.n))
+    throw Error(NZCB_ERR_ARG, "msm scratch was not sized for the segment plan");
   if (table && ((size_t)p.nb / kTileSide * msets > sc.rowp29.n ||
                 (((size_t)1 << p.hb) + ((size_t)1 << p.a)) * msets > sc.lines29.n ||
                 (size_t)(p.lb + 1) * msets > sc.host_win_cap || (msets > 1 && p.c >= kStripMinC)))
@@ -1760,6 +2001,7 @@ static void msm_enqueue_impl(MsmScratch& sc, const G1Affine* bases, const Fr* co
   sc.cur_seglen = p.seglen;
   sc.cur_nkeys = p.nkeys;
   sc.cur_fixed = table != nullptr;
+  sc.cur_seg = seg;
   sc.cur_a = p.a;
   sc.cur_hb = p.hb;
   sc.cur_msets = p.msets;
@@ -1789,6 +2031,22 @@ static void msm_enqueue_impl(MsmScratch& sc, const G1Affine* bases, const Fr* co
                        dim3(kMsmThreads), 0, st, sc.keys_out.p, p.entries, p.nkeys, sc.offsets.p);
     NZ_HIP(hipGetLastError());
   }
+  const SegPlan pl{sc.seg_start.p, sc.seg_len.p, sc.seg_bucket.p, sc.seg_dst.p,
+                   sc.seg_mk.p,    sc.seg_mfs.p, sc.seg_mnp.p,   sc.seg_meta.p};
+  if (seg) {  // the plan, from the offsets just written (its time counts as the offsets phase)
+    const uint32_t ntiles = (uint32_t)seg_tiles(p.nkeys);
+    const dim3 tgrid((ntiles + kSegWaves - 1) / kSegWaves);
+    hipLaunchKernelGGL(msm_seg_hist_kernel, tgrid, dim3(kSegThreads), 0, st, (const uint32_t*)sc.offsets.p, p.nkeys,
+                       ntiles, sc.seg_cnt.p, sc.seg_meta.p);
+    NZ_HIP(hipGetLastError());
+    hipLaunchKernelGGL(msm_bin_rowscan_kernel, dim3(kSegMax), dim3(256), 0, st, sc.seg_cnt.p, ntiles,
+                       sc.seg_cnt.p + (size_t)kSegMax * ntiles);
+    NZ_HIP(hipGetLastError());
+    hipLaunchKernelGGL(msm_seg_scatter_kernel, tgrid, dim3(kSegThreads), 0, st, (const uint32_t*)sc.offsets.p, p.nkeys,
+                       ntiles, (const uint32_t*)sc.seg_cnt.p, pl);
+    NZ_HIP(hipGetLastError());
+    lmark("mark: L seg_plan");
+  }
   if (sc.prof) NZ_HIP(hipEventRecord(sc.ev[3], st));
   // sparse tables: chunk 0 = derived on the device from the bucketed entry count (dyn_chunk);
   // the grid covers the most threads any count can ask for
@@ -1798,7 +2056,12 @@ static void msm_enqueue_impl(MsmScratch& sc, const G1Affine* bases, const Fr* co
   const size_t nthreads = sparse ? dyn_threads_bound(p.entries) : (p.entries + chunk - 1) / chunk;
   const dim3 agrid(grid_for(nthreads, kMsmThreads, 1u << 30));
   const G1Affine* gather = table ? table->q.p : bases;
-  if (table) {
+  if (seg) {
+    const dim3 sgrid(grid_for(seg_bound(p.entries, p.nkeys), kMsmThreads, 1u << 30));  // waves past the plan return
+    hipLaunchKernelGGL(msm_accumulate29_seg_kernel, sgrid, dim3(kMsmThreads), 0, st, gather, (const uint32_t*)sc.sorted.p,
+                       (const uint32_t*)pl.start, (const uint32_t*)pl.len, (const uint32_t*)pl.dst,
+                       (const uint32_t*)pl.meta, sc.buckets29.p, sc.carry_own29.p, sc.carry_cont29.p);
+  } else if (table) {
     if (chunk == kChunk || sparse)  // sparse: chunk <= kChunk
       hipLaunchKernelGGL(msm_accumulate29_kernel<true>, agrid, dim3(kMsmThreads), 0, st, chunk, gather, sc.sorted.p,
                          sc.offsets.p, p.nkeys, nthreads, sc.buckets29.p, sc.carry_own29.p, sc.carry_cont29.p);
@@ -1814,28 +2077,35 @@ static void msm_enqueue_impl(MsmScratch& sc, const G1Affine* bases, const Fr* co
   if (sc.prof) NZ_HIP(hipEventRecord(sc.ev[4], st));
   const dim3 fgrid(grid_for(p.nkeys, kMsmThreads, 1u << 30));
   if (table) {  // the large list's count was zeroed by msm_lo_scan_kernel
-    hipLaunchKernelGGL(msm_finalize29_kernel, fgrid, dim3(kMsmThreads), 0, st, chunk, sc.offsets.p, p.nkeys,
-                       sparse ? kSeqSpanSparse : kSeqSpan29, (const Xyzz29*)sc.carry_own29.p,
-                       (const Xyzz29*)sc.carry_cont29.p, sc.large.p, sc.buckets29.p);
-    NZ_HIP(hipGetLastError());
-    lmark("mark: L finalize");
-    hipLaunchKernelGGL(msm_large_scan_kernel, dim3(1), dim3(1024), 0, st, chunk, sc.offsets.p, p.nkeys, sc.large.p,
-                       sc.large_off.p);
-    NZ_HIP(hipGetLastError());
-    lmark("mark: L large_scan");
-    hipLaunchKernelGGL(msm_large_piece29_kernel, dim3(sparse ? kSparsePieceBlocks : kLargePieceBlocks),
-                       dim3(kSumThreads), 0, st, chunk, sc.offsets.p, p.nkeys, sc.large.p, sc.large_off.p,
-                       (const Xyzz29*)sc.carry_own29.p, (const Xyzz29*)sc.carry_cont29.p, sc.large_part.p);
-    NZ_HIP(hipGetLastError());
-    lmark("mark: L piece");
-    if (sparse)
-      hipLaunchKernelGGL(msm_large_final29_kernel<kSumThreads>, dim3(kSparseFinalBlocks), dim3(kSumThreads), 0, st,
-                         sc.large.p, sc.large_off.p, sc.large_part.p, sc.buckets29.p);
-    else
-      hipLaunchKernelGGL(msm_large_final29_kernel<64>, dim3(kLargeFinalBlocks), dim3(64), 0, st, sc.large.p,
-                         sc.large_off.p, sc.large_part.p, sc.buckets29.p);
-    NZ_HIP(hipGetLastError());
-    lmark("mark: L final");
+    auto finalize = [&](auto kseg) {
+      constexpr bool kSeg = decltype(kseg)::value;
+      // segments: a thread per bucket cut into pieces (none for random scalars at kSegMax = 256)
+      const dim3 grid = kSeg ? dim3(grid_for(seg_multi_bound(p.entries, p.nkeys) + 1, kMsmThreads, 1u << 30)) : fgrid;
+      hipLaunchKernelGGL(msm_finalize29_kernel<kSeg>, grid, dim3(kMsmThreads), 0, st, chunk, sc.offsets.p, p.nkeys,
+                         sparse ? kSeqSpanSparse : kSeqSpan29, (const Xyzz29*)sc.carry_own29.p,
+                         (const Xyzz29*)sc.carry_cont29.p, sc.large.p, sc.buckets29.p, pl);
+      NZ_HIP(hipGetLastError());
+      lmark("mark: L finalize");
+      hipLaunchKernelGGL(msm_large_scan_kernel<kSeg>, dim3(1), dim3(1024), 0, st, chunk, sc.offsets.p, p.nkeys,
+                         sc.large.p, sc.large_off.p, pl);
+      NZ_HIP(hipGetLastError());
+      lmark("mark: L large_scan");
+      hipLaunchKernelGGL(msm_large_piece29_kernel<kSeg>, dim3(sparse ? kSparsePieceBlocks : kLargePieceBlocks),
+                         dim3(kSumThreads), 0, st, chunk, sc.offsets.p, p.nkeys, sc.large.p, sc.large_off.p,
+                         (const Xyzz29*)sc.carry_own29.p, (const Xyzz29*)sc.carry_cont29.p, sc.large_part.p, pl);
+      NZ_HIP(hipGetLastError());
+      lmark("mark: L piece");
+      if (sparse)
+        hipLaunchKernelGGL((msm_large_final29_kernel<kSumThreads, kSeg>), dim3(kSparseFinalBlocks), dim3(kSumThreads),
+                           0, st, sc.large.p, sc.large_off.p, sc.large_part.p, sc.buckets29.p,
+                           (const uint32_t*)pl.mk);
+      else
+        hipLaunchKernelGGL((msm_large_final29_kernel<64, kSeg>), dim3(kLargeFinalBlocks), dim3(64), 0, st, sc.large.p,
+                           sc.large_off.p, sc.large_part.p, sc.buckets29.p, (const uint32_t*)pl.mk);
+      NZ_HIP(hipGetLastError());
+      lmark("mark: L final");
+    };
+    if (seg) finalize(std::true_type()); else finalize(std::false_type());
     mark(5);
     int lparts = p.ltiles, hparts = p.htiles;  // partials per row / per column
     if (p.c >= kStripMinC) {
@@ -1890,6 +2160,26 @@ static void msm_enqueue_impl(MsmScratch& sc, const G1Affine* bases, const Fr* co
   NZ_HIP(hipMemcpyAsync(sc.host_win, sc.win.p, (size_t)p.nsets * p.nslots * sizeof(G1xyzz), hipMemcpyDeviceToHost,
                         st));
   NZ_HIP(hipEventRecord(sc.done, st));
+}
+
+bool msm_debug_plan(MsmScratch& sc, hipStream_t st, std::vector<uint32_t>& offsets, std::vector<uint32_t>& start,
+                    std::vector<uint32_t>& len, std::vector<uint32_t>& bucket) {
+  if (!sc.cur_fixed || !sc.cur_seg || sc.cur_n == 0) return false;
+  NZ_HIP(hipStreamSynchronize(st));
+  uint32_t meta[2] = {0, 0};
+  NZ_HIP(hipMemcpy(meta, sc.seg_meta.p, sizeof(meta), hipMemcpyDeviceToHost));
+  if (meta[0] > sc.seg_start.n) throw Error(NZCB_ERR_INTERNAL, "segment plan larger than its bound");
+  offsets.resize((size_t)sc.cur_nkeys + 1);
+  start.resize(meta[0]);
+  len.resize(meta[0]);
+  bucket.resize(meta[0]);
+  NZ_HIP(hipMemcpy(offsets.data(), sc.offsets.p, offsets.size() * 4, hipMemcpyDeviceToHost));
+  if (meta[0]) {
+    NZ_HIP(hipMemcpy(start.data(), sc.seg_start.p, (size_t)meta[0] * 4, hipMemcpyDeviceToHost));
+    NZ_HIP(hipMemcpy(len.data(), sc.seg_len.p, (size_t)meta[0] * 4, hipMemcpyDeviceToHost));
+    NZ_HIP(hipMemcpy(bucket.data(), sc.seg_bucket.p, (size_t)meta[0] * 4, hipMemcpyDeviceToHost));
+  }
+  return true;
 }
 
 void msm_enqueue(MsmScratch& sc, const G1Affine* bases, const Fr* scalars, size_t n, bool mont, hipStream_t st,

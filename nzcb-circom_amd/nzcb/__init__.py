@@ -45,7 +45,7 @@ EXPORTED_SYMBOLS = [
     "nzcb_nzcp_witness_dev", "nzcb_synth_setup_ex", "nzcb_memcpy_d2d",
     "nzcb_plonk_setup", "nzcb_prove_batch_status", "nzcb_wprog_remap", "nzcb_prove_logged", "nzcb_memcpy_d2d_async",
     "nzcb_debug_guard_check", "nzcb_debug_guard_selftest", "nzcb_debug_inject_fault", "nzcb_debug_f29",
-    "nzcb_debug_ntt_coset",
+    "nzcb_debug_ntt_coset", "nzcb_debug_msm_plan",
     "nzcb_msm_table_create_lagrange",
     "nzcb_verify_batch", "nzcb_engine_g1_lincomb", "nzcb_engine_verify_batch", "nzcb_debug_verify_batch_timings",
     "nzcb_r1cs_create", "nzcb_r1cs_create_file", "nzcb_r1cs_info", "nzcb_r1cs_check", "nzcb_r1cs_destroy",
@@ -241,6 +241,9 @@ def load(path: str | None = None):
                                               c_int, u8p, POINTER(_Err)]),
         "nzcb_engine_msm_sets_dev": (c_int, [c_void_p, c_void_p, c_size_t, POINTER(c_void_p), c_int, c_size_t, c_int,
                                              c_int, u8p, POINTER(_Err)]),
+        "nzcb_debug_msm_plan": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_int, c_int, c_int,
+                                        POINTER(c_uint32), POINTER(c_uint32), c_size_t, POINTER(c_uint32), c_size_t,
+                                        u8p, POINTER(_Err)]),
         "nzcb_plonk_setup": (c_int, [ctypes.c_char_p, c_size_t, ctypes.c_char_p, c_size_t, c_int, POINTER(POINTER(c_uint8)),
                                      POINTER(c_size_t), POINTER(_Err)]),
         "nzcb_nzcp_input_signals": (c_size_t, [POINTER(NzcpParams)]),
@@ -596,6 +599,26 @@ class Engine:
             _check(self.lib.nzcb_engine_msm_fixed_dev(self.h, dev_bases, n_table, dev_scalars, n, int(scalars_mont),
                                                       out, ctypes.byref(err)), err)
         return bytes(out)
+
+    def msm_plan(self, dev_bases: int, n_table: int, dev_scalars: int, n: int, scalars_mont: bool, window: int = 0,
+                 fold: bool = False):
+        """msm_fixed_dev's dense MSM together with the segment plan it accumulated by
+        (include/nzcb_internal.h nzcb_debug_msm_plan): (result, plan), plan = None when the MSM ran
+        in chunks (NZCB_ACC_SEGMENTS=0), else a dict of seg_max and the lists offsets (buckets + 1),
+        start, len and bucket of the segments in plan order."""
+        c = window or 20
+        off_cap = (1 << (c - 1)) + 1
+        seg_cap = 3 * (n * ((255 + c - 1) // c) + 1)
+        info, off, seg = (c_uint32 * 4)(), (c_uint32 * off_cap)(), (c_uint32 * seg_cap)()
+        out = _out(64)
+        err = _Err()
+        _check(self.lib.nzcb_debug_msm_plan(self.h, dev_bases, n_table, dev_scalars, n, int(scalars_mont), int(window),
+                                            int(fold), info, off, off_cap, seg, seg_cap, out, ctypes.byref(err)), err)
+        if not info[0]:
+            return bytes(out), None
+        nk, ns = info[1], info[2]
+        return bytes(out), {"seg_max": info[3], "offsets": off[:nk + 1], "start": seg[:ns], "len": seg[ns:2 * ns],
+                            "bucket": seg[2 * ns:3 * ns]}
 
     def msm_sets_dev(self, dev_bases: int, n_table: int, dev_scalars: list, n: int, scalars_mont: bool, *,
                      sparse: bool) -> list:
