@@ -522,6 +522,97 @@ int nzcb_plonk_setup(const uint8_t* r1cs, size_t r1cs_len, const uint8_t* ptau, 
 int nzcb_ptau_synth(int power, const uint8_t* tau, int device, uint8_t** ptau_out, size_t* ptau_len, nzcb_err* err);
 void nzcb_free(void* p);
 
+/* ---- Key material check (csrc/key_check.h, csrc/key_check.hip) --------------------------- */
+/* Is a powers-of-tau file what it claims to be: P_i = [tau^i]G1 for the tau of its [tau]G2?
+ * nzcb_plonk_setup copies its points into the key untested, and a wrong point shows up only as
+ * "Invalid proof" later. The steps run in this order and the first that fails sets the
+ * finding:
+ *   G2        T = tauG2[1] has a stored coordinate >= q, is the point at infinity, is not on
+ *             the twist, or [r]T != O (host, once);
+ *   points    every P_i: a stored coordinate >= q (RANGE), or (0, 0) or y^2 != x^3 + 3
+ *             (CURVE). status is that of the lowest defective point, index is that point and
+ *             n_bad counts all defective points;
+ *   generator P_0 != (1, 2), or tauG2[0] is not the G2 generator (index 0);
+ *   sequence  with weights rho_i, L = sum rho_i P_i and R = sum rho_i P_(i+1) over
+ *             0 <= i < m - 1 (two MSMs on the GPU): e(-L, T) e(R, [1]_2) = 1. When that fails,
+ *             index is the lowest i >= 1 with P_i != tau P_(i-1), found by bisection with
+ *             sub-sums of the same terms: pairing_checks is 1 on the clean path and at most
+ *             2 + ceil(log2 m) on a failing one. A wrong file passes a check with probability
+ *             of order 2^-128.
+ * rho_i is the low 128 bits of keccak256(seed || LE32(i)) (the digest read as a big-endian
+ * integer; zero becomes 1), nzcb_verify_batch's rule. seed = NULL draws a 32-byte seed from the
+ * OS CSPRNG. A caller-given seed is FOR REPRODUCIBLE TESTS ONLY: whoever knows the weights
+ * before making the file can make wrong points cancel.
+ * The points go through the GPU in chunks that overlap by one point, so HBM use does not grow
+ * with the file. device = NZCB_KEY_HOST runs the same steps on the host (no speed target);
+ * the findings are the same. A call owns its stream and buffers, needs no nzcb_ctx and may run
+ * while a context proves on the same device.
+ * NOT examined: the ceremony's contributions (what snarkjs `powersoftau verify` audits), the
+ * alpha and beta sections, the Lagrange sections and tauG2 past [tau]G2. */
+#define NZCB_KEY_HOST (-1)
+enum {
+  NZCB_KEY_OK = 0,
+  NZCB_KEY_ERR_G2,
+  NZCB_KEY_ERR_RANGE,
+  NZCB_KEY_ERR_CURVE,
+  NZCB_KEY_ERR_GENERATOR,
+  NZCB_KEY_ERR_SEQUENCE,
+  NZCB_KEY_ERR_COSETS,       /* zkey findings from here on */
+  NZCB_KEY_ERR_NONCANONICAL,
+  NZCB_KEY_ERR_LAGRANGE,
+  NZCB_KEY_ERR_EVALS,
+  NZCB_KEY_ERR_COMMIT
+};
+typedef struct nzcb_key_finding {
+  int32_t status;          /* NZCB_KEY_* */
+  uint32_t pairing_checks; /* pairing checks the call ran; a zkey part: commit_checked, 1 if rule 4 ran */
+  uint64_t index;          /* the point the status speaks of (0 when it names none) */
+  uint64_t n_bad;          /* RANGE / CURVE: all defective points */
+  uint64_t checked;        /* points examined */
+} nzcb_key_finding;
+/* ptau: header (section 1: n8 = 32, q, power), tauG1 (section 2) and tauG2 (section 3); other
+ * sections are ignored. count = 0 checks every point the header promises, 2^(power+1) - 1;
+ * otherwise the first `count` (a circuit of domain 2^p uses 2^p + 6). Returns 0 with the
+ * verdict in *out whatever the content says; NZCB_ERR_FORMAT for a missing or short section,
+ * NZCB_ERR_ARG for a count larger than section 2 holds. */
+int nzcb_ptau_check(const uint8_t* ptau, size_t len, uint64_t count, int device /* >= 0, or NZCB_KEY_HOST */,
+                    const uint8_t* seed /* 32 B or NULL */, nzcb_key_finding* out, nzcb_err* err);
+/* The same from a file, memory-mapped (a power-28 ptau is 34 GB). */
+int nzcb_ptau_check_file(const char* path, uint64_t count, int device, const uint8_t* seed, nzcb_key_finding* out,
+                         nzcb_err* err);
+/* Is a PLONK zkey consistent with itself? A truncated download or a flipped bit in its
+ * evaluations loads without complaint today and surfaces as "Invalid proof" or "T Polynomial
+ * is not divisible". The file is parsed as nzcb_ctx_create parses it (its errors are this
+ * call's non-zero returns); every verdict about the content returns 0:
+ *   header_srs[0]  NZCB_KEY_ERR_COSETS when k1^n = 1, k2^n = 1 or (k2 / k1)^n = 1 (or one is
+ *                  zero): <w>, k1 <w>, k2 <w> are then not three disjoint cosets.
+ *                  NZCB_KEY_ERR_NONCANONICAL when k1 (index 0) or k2 (index 1) is stored >= r;
+ *   header_srs[1]  the check of nzcb_ptau_check over section 14's n + 6 points against the
+ *                  header's X_2;
+ *   parts[0..7]    Qm, Ql, Qr, Qo, Qc, S1, S2, S3, then parts[8 + j], the max(nPublic, 1)
+ *                  Lagrange polynomials. Each is n coefficients and 4n evaluations; every part
+ *                  is examined whatever the others say and its status is the first rule it fails:
+ *     NONCANONICAL one of its 5n stored values is >= r (index: the lowest, in 0..5n; n_bad: all);
+ *     LAGRANGE     Lagrange parts only: the n-point transform of the coefficients is not the
+ *                  unit vector e_j (index: the lowest mismatch; n_bad: all);
+ *     EVALS        the 4n stored evaluations are not byte-equal to the 4n-point transform of
+ *                  the coefficients padded with zeros, which is what `plonk setup` writes
+ *                  (index: the lowest mismatch; n_bad: the number of mismatches);
+ *     COMMIT       parts 0..7 only, and only when header_srs[1] is OK: the header's point is
+ *                  not the MSM of the coefficients over PTau[0..n). pairing_checks records
+ *                  whether this rule ran (commit_checked).
+ * parts_cap findings are written at most; *n_parts is always 8 + max(nPublic, 1). *ok = 1 iff
+ * every finding is NZCB_KEY_OK. device and seed as for nzcb_ptau_check.
+ * OUT OF SCOPE: whether sigma is the permutation of YOUR circuit, the A/B/C maps and the
+ * additions; they need the r1cs. Regenerating the key with `plonk setup` and comparing remains
+ * the way to check those. */
+int nzcb_zkey_check(const uint8_t* zkey, size_t len, int device, const uint8_t* seed, int* ok,
+                    nzcb_key_finding* header_srs /* [2] */, nzcb_key_finding* parts, uint32_t parts_cap,
+                    uint32_t* n_parts, nzcb_err* err);
+/* The same from a file, memory-mapped (nzcp_live's zkey is ~3.9 GB). */
+int nzcb_zkey_check_file(const char* path, int device, const uint8_t* seed, int* ok, nzcb_key_finding* header_srs,
+                         nzcb_key_finding* parts, uint32_t parts_cap, uint32_t* n_parts, nzcb_err* err);
+
 /* ---- HBM buffers (witnesses for nzcb_prove_device / nzcb_prove_batch on device) ---- */
 void* nzcb_dev_alloc(size_t bytes);
 /* The same on `device`; the calling thread's current device is left as it was (the N-API

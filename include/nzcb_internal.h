@@ -217,6 +217,24 @@ int nzcb_debug_p256_timings(double* ms, int cap);
  * 0 on the host path), [1] the call's wall time. Returns the number of values written (cap <= 2). */
 int nzcb_debug_nzcp_decode_timings(double* ms, int cap);
 
+/* ---- Key material check (csrc/key_check.h, csrc/key_check.hip) -------------------------- */
+/* The check behind nzcb_ptau_check (nzcb.h) on bare arrays: points = m x 64 B (x || y, LE
+ * Montgomery: ptau section 2, zkey section 14), m >= 1; g2 = 128 B, the layout of X_2; seed as
+ * there. chunk_points: points per device chunk with the one overlap point (0 = the library's
+ * constant, otherwise 2..2^22); the finding does not depend on it. lr_out (may be NULL): L || R
+ * of the whole range, affine, 32-byte LE normal form, zeros for infinity or when an earlier
+ * step ended the check. */
+int nzcb_engine_srs_check(int device, const uint8_t* points, uint64_t m, const uint8_t* g2, const uint8_t* seed,
+                          uint32_t chunk_points, nzcb_key_finding* finding, uint8_t* lr_out /* 128 B */,
+                          nzcb_err* err);
+/* Milliseconds of the calling thread's last key check: [0] the point kernel, [1] the weight
+ * kernel, [2] the two MSMs (wall, with their host part), [3] host-to-device copies and the
+ * rest of the device pass (wall), [4] the pairing checks on the host, [5] the call, and for a
+ * zkey [6] the transforms, [7] the compare kernel, [8] the commitments' MSMs (wall). Kernel
+ * times are HIP events; 0 on the host path except [4] and [5]. Returns the number written
+ * (cap <= 9). */
+int nzcb_debug_key_check_timings(double* ms, int cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -217,6 +217,13 @@ F12 miller_loop(const P2& q, const G1Affine& p) {
 
 }  // namespace
 
+P2 p2_sum(const P2& a, const P2& b) { return p2_add(a, b); }
+
+bool p2_on_twist(const P2& p) {
+  static const F2 b2 = f2_mul({fq_small(3), Fq::zero()}, f2_inv({fq_small(9), Fq::one()}));
+  return f2_eq(f2_mul(p.y, p.y), f2_add(f2_mul(f2_mul(p.x, p.x), p.x), b2));
+}
+
 bool pairing_check(const std::vector<std::pair<G1Affine, P2>>& pairs) {
   F12 f = f12_one();
   for (const auto& pq : pairs) f = f12_mul(f, miller_loop(pq.second, pq.first));

@@ -32,6 +32,10 @@ struct Vk {
 };
 Vk vk_read(const uint8_t* in, bool* ok);
 P2 g2_generator();
+// G2 on the host for the key check (csrc/key_check.hip): the sum of two points, and whether a
+// finite point satisfies the twist's equation y^2 = x^3 + 3 / (9 + u)
+P2 p2_sum(const P2& a, const P2& b);
+bool p2_on_twist(const P2& p);
 
 // prod e(P_i, Q_i) == 1
 bool pairing_check(const std::vector<std::pair<G1Affine, P2>>& pairs);

@@ -794,6 +794,140 @@ napi_value WtnsCheck(napi_env env, napi_callback_info info) {
   return promise;
 }
 
+// one powersOfTau.check / zKey.check call (nzcb_ptau_check*, nzcb_zkey_check*) on a worker thread
+// (async work); the promise is settled on the main thread. A file name is memory-mapped by the
+// library; a Buffer is copied.
+struct KeyCheckWork {
+  napi_deferred deferred = nullptr;
+  napi_async_work work = nullptr;
+  bool zkey = false, from_file = false;
+  std::string path;
+  std::vector<uint8_t> data;
+  int device = 0;
+  uint64_t count = 0;
+  nzcb_key_finding ptau{};
+  int ok = 0;
+  nzcb_key_finding header_srs[2] = {};
+  std::vector<nzcb_key_finding> parts;
+  uint32_t n_parts = 0;
+  int rc = 0;
+  nzcb_err err{};
+};
+
+void key_check_execute(napi_env, void* data) {
+  KeyCheckWork* w = static_cast<KeyCheckWork*>(data);
+  if (!w->zkey) {
+    w->rc = w->from_file ? nzcb_ptau_check_file(w->path.c_str(), w->count, w->device, nullptr, &w->ptau, &w->err)
+                         : nzcb_ptau_check(w->data.data(), w->data.size(), w->count, w->device, nullptr, &w->ptau,
+                                           &w->err);
+    return;
+  }
+  w->parts.assign(8 + 64, nzcb_key_finding{});
+  for (int pass = 0; pass < 2; pass++) {  // again only when the key has more parts than fit
+    const uint32_t cap = (uint32_t)w->parts.size();
+    w->rc = w->from_file ? nzcb_zkey_check_file(w->path.c_str(), w->device, nullptr, &w->ok, w->header_srs,
+                                                w->parts.data(), cap, &w->n_parts, &w->err)
+                         : nzcb_zkey_check(w->data.data(), w->data.size(), w->device, nullptr, &w->ok, w->header_srs,
+                                           w->parts.data(), cap, &w->n_parts, &w->err);
+    if (w->rc != 0 || w->n_parts <= cap) break;
+    w->parts.assign(w->n_parts, nzcb_key_finding{});
+  }
+}
+
+napi_value key_finding_object(napi_env env, const nzcb_key_finding& f, bool part) {
+  static const char* const names[] = {"OK", "G2", "RANGE", "CURVE", "GENERATOR", "SEQUENCE", "COSETS",
+                                      "NONCANONICAL", "LAGRANGE", "EVALS", "COMMIT"};
+  napi_value out, v;
+  napi_create_object(env, &out);
+  napi_create_string_utf8(env, f.status >= 0 && f.status <= NZCB_KEY_ERR_COMMIT ? names[f.status] : "?",
+                          NAPI_AUTO_LENGTH, &v);
+  napi_set_named_property(env, out, "status", v);
+  napi_create_double(env, (double)f.index, &v);
+  napi_set_named_property(env, out, "index", v);
+  napi_create_double(env, (double)f.n_bad, &v);
+  napi_set_named_property(env, out, "nBad", v);
+  napi_create_double(env, (double)f.checked, &v);
+  napi_set_named_property(env, out, "checked", v);
+  if (part) {
+    napi_get_boolean(env, f.pairing_checks != 0, &v);
+    napi_set_named_property(env, out, "commitChecked", v);
+  } else {
+    napi_create_uint32(env, f.pairing_checks, &v);
+    napi_set_named_property(env, out, "pairingChecks", v);
+  }
+  return out;
+}
+
+void key_check_complete(napi_env env, napi_status status, void* data) {
+  KeyCheckWork* w = static_cast<KeyCheckWork*>(data);
+  if (status != napi_ok || w->rc != 0) {
+    napi_reject_deferred(env, w->deferred,
+                         make_error(env, w->rc ? w->err.code : NZCB_ERR_INTERNAL,
+                                    w->rc ? w->err.msg : "keyCheck: the work was cancelled"));
+  } else if (!w->zkey) {
+    napi_resolve_deferred(env, w->deferred, key_finding_object(env, w->ptau, false));
+  } else {
+    static const char* const part_names[8] = {"Qm", "Ql", "Qr", "Qo", "Qc", "S1", "S2", "S3"};
+    napi_value out, ok, parts;
+    napi_create_object(env, &out);
+    napi_get_boolean(env, w->ok != 0, &ok);
+    napi_set_named_property(env, out, "ok", ok);
+    napi_set_named_property(env, out, "header", key_finding_object(env, w->header_srs[0], false));
+    napi_set_named_property(env, out, "srs", key_finding_object(env, w->header_srs[1], false));
+    napi_create_object(env, &parts);
+    for (uint32_t k = 0; k < w->n_parts && k < w->parts.size(); k++) {
+      const std::string name = k < 8 ? part_names[k] : "L" + std::to_string(k - 8);
+      napi_set_named_property(env, parts, name.c_str(), key_finding_object(env, w->parts[k], true));
+    }
+    napi_set_named_property(env, out, "parts", parts);
+    napi_resolve_deferred(env, w->deferred, out);
+  }
+  napi_delete_async_work(env, w->work);
+  delete w;
+}
+
+// keyCheck(kind: 0 = ptau | 1 = zkey, file: string (file name) | Buffer, device: number, count: number)
+//   -> Promise<finding> (ptau) or Promise<{ok, header, srs, parts: {Qm: finding, ..., L0: ...}}> (zkey);
+//   finding = {status: 'OK' | 'G2' | ..., index, nBad, checked, pairingChecks | commitChecked}
+napi_value KeyCheck(napi_env env, napi_callback_info info) {
+  size_t argc = 4;
+  napi_value argv[4];
+  CHECK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  KeyCheckWork* w = new KeyCheckWork();
+  const uint8_t* b = nullptr;
+  size_t bl = 0;
+  int32_t kind = -1, device = 0;
+  double count = 0;
+  bool ok = argc >= 2 && napi_get_value_int32(env, argv[0], &kind) == napi_ok && (kind == 0 || kind == 1);
+  if (ok && str_arg(env, argv[1], &w->path)) {
+    w->from_file = true;
+  } else if (ok && buf_arg(env, argv[1], &b, &bl)) {
+    w->data.assign(b, b + bl);
+  } else {
+    ok = false;
+  }
+  if (argc > 2) napi_get_value_int32(env, argv[2], &device);
+  if (argc > 3) napi_get_value_double(env, argv[3], &count);
+  if (!ok || count < 0 || count > 4294967295.0) {
+    delete w;
+    napi_throw_type_error(env, nullptr, "keyCheck(kind: 0 | 1, file: string | Buffer, device?, count?)");
+    return nullptr;
+  }
+  w->zkey = kind == 1;
+  w->device = device;
+  w->count = (uint64_t)count;
+  napi_value promise, name;
+  if (napi_create_promise(env, &w->deferred, &promise) != napi_ok ||
+      napi_create_string_utf8(env, "nzcb.keyCheck", NAPI_AUTO_LENGTH, &name) != napi_ok ||
+      napi_create_async_work(env, nullptr, name, key_check_execute, key_check_complete, w, &w->work) != napi_ok ||
+      napi_queue_async_work(env, w->work) != napi_ok) {
+    delete w;
+    napi_throw_error(env, nullptr, "nzcb addon: N-API call failed");
+    return nullptr;
+  }
+  return promise;
+}
+
 // one p256Verify call: the key's tables built (nzcb_p256_key_create), the batch verified
 // (nzcb_p256_verify) and the key released, on a worker thread (async work); the promise is
 // settled on the main thread. The inputs are copied.
@@ -1177,6 +1311,7 @@ napi_value Init(napi_env env, napi_value exports) {
       {"setLanes", nullptr, SetLanes, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"releaseContext", nullptr, ReleaseContext, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"wtnsCheck", nullptr, WtnsCheck, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"keyCheck", nullptr, KeyCheck, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"r1csInfo", nullptr, R1csInfo, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"p256Verify", nullptr, P256Verify, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"nzcpDecode", nullptr, NzcpDecode, nullptr, nullptr, nullptr, napi_default, nullptr},

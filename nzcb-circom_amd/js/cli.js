@@ -16,6 +16,11 @@
 //     (prints "WITNESS IS CORRECT" and exits 0, or "WITNESS CHECKING FAILED" with the failing
 //     constraints and exit code 1; NZCB_DEVICE=-1 checks on the host)
 //   node cli.js r1cs info  <circuit.r1cs>
+// and the key material examined before use (not snarkjs's `powersoftau verify`, which audits the
+// ceremony's contributions):
+//   node cli.js powersoftau check <pot.ptau> [power]
+//   node cli.js zkey check <circuit.zkey>
+//     (one line per finding; exit code 0 only when everything is OK; NZCB_DEVICE=-1 checks on the host)
 // and the signature check of NZ COVID Passes (what verifyPassURIOffline does in the reference's tests):
 //   node cli.js nzcp verify <file with one pass URI per line> [example | <x> <y>]
 //     (the issuer's P-256 key as base64url JWK coordinates, default the specification's example
@@ -34,6 +39,8 @@ function usage() {
                 '       cli.js zkey export solidityverifier <zkey> <verifier.sol> [contract name]\n' +
                 '       cli.js zkey export soliditycalldata <public.json> <proof.json>\n' +
                 '       cli.js wtns check <r1cs> <wtns>\n' +
+                '       cli.js powersoftau check <ptau> [power]\n' +
+                '       cli.js zkey check <zkey>\n' +
                 '       cli.js r1cs info <r1cs>\n' +
                 '       cli.js nzcp verify <file with one pass URI per line> [example | <x> <y>]');
   process.exit(1);
@@ -56,7 +63,22 @@ async function zkeyExport(argv) {
   }
 }
 
+async function keyCheck(argv) {
+  const say = { info: (m) => console.log(m) };
+  const device = process.env.NZCB_DEVICE === undefined ? 0 : Number(process.env.NZCB_DEVICE);
+  if (argv[0] === 'zkey') {
+    const r = await nz.zKey.check(argv[2], say, { device });
+    process.exit(r.ok ? 0 : 1);
+  }
+  const power = argv.length === 4 ? Number(argv[3]) : undefined;
+  if (power !== undefined && !(Number.isInteger(power) && power >= 0 && power <= 28)) usage();
+  const f = await nz.powersOfTau.check(argv[2], say, { device, power });
+  process.exit(f.status === 'OK' ? 0 : 1);
+}
+
 async function main(argv) {
+  if (argv[0] === 'zkey' && argv[1] === 'check' && argv.length === 3) return keyCheck(argv);
+  if (argv[0] === 'powersoftau' && argv[1] === 'check' && (argv.length === 3 || argv.length === 4)) return keyCheck(argv);
   if (argv[0] === 'zkey') return zkeyExport(argv);
   if (argv[0] === 'wtns' && argv[1] === 'check' && argv.length === 4) {
     const say = { info: (m) => console.log(m), warn: (m) => console.log(m), debug: () => {} };

@@ -497,6 +497,47 @@ async function wtnsCheck(r1csFileName, wtnsFileName, logger, options) {
   return false;
 }
 
+// Key material examined on the GPU before use (include/nzcb.h nzcb_ptau_check, nzcb_zkey_check),
+// on a worker thread; a file name is memory-mapped, a Buffer is copied. The names are `check`,
+// not `verify`: snarkjs's `powersoftau verify` audits the ceremony's contributions, and this
+// does not.
+// powersOfTau.check(ptau, logger, {device (default 0; -1 = on the host), power}): every tauG1 point
+// on the curve, P_0 the generator and P_i = tau P_(i-1) against the file's [tau]G2. With `power`
+// only the 2^power + 6 points a circuit of that domain uses. Resolves to the finding
+// {status: 'OK' | 'G2' | 'RANGE' | 'CURVE' | 'GENERATOR' | 'SEQUENCE', index, nBad, checked,
+// pairingChecks} and logs one line.
+function findingLine(name, f) {
+  if (f.status === 'OK') return `${name}: OK (${f.checked} checked)`;
+  const bad = f.nBad ? `, ${f.nBad} defective` : '';
+  return `${name}: ${f.status} at ${f.index}${bad}`;
+}
+function keyFile(f) {
+  return typeof f === 'string' ? f : readBin(f);
+}
+async function powersOfTauCheck(ptau, logger, options) {
+  options = options || {};
+  const info = logger && typeof logger.info === 'function' ? (m) => logger.info(m) : loggerFn(logger);
+  const count = options.power === undefined ? 0 : Math.pow(2, options.power) + 6;
+  const f = await addon.keyCheck(0, keyFile(ptau), options.device === undefined ? 0 : options.device, count);
+  if (info) info(findingLine('tauG1', f));
+  return f;
+}
+// zKey.check(zkey, logger, {device}): the key's cosets, its PTau against X_2, and per polynomial
+// the canonical values, the evaluations against the coefficients and the header's commitment.
+// Resolves to {ok, header, srs, parts: {Qm, ..., S3, L0, ...}} and logs one line per finding.
+// Whether the key belongs to your circuit is not examined: that needs the r1cs.
+async function zKeyCheck(zkey, logger, options) {
+  options = options || {};
+  const info = logger && typeof logger.info === 'function' ? (m) => logger.info(m) : loggerFn(logger);
+  const r = await addon.keyCheck(1, keyFile(zkey), options.device === undefined ? 0 : options.device, 0);
+  if (info) {
+    info(findingLine('k1, k2', r.header));
+    info(findingLine('PTau', r.srs));
+    for (const name of Object.keys(r.parts)) info(findingLine(name, r.parts[name]));
+  }
+  return r;
+}
+
 // snarkjs r1cs.info(r1csFileName): the circuit's sizes (host only, no GPU)
 async function r1csInfo(r1csFileName, logger) {
   const v = addon.r1csInfo(r1csFileName);
@@ -777,7 +818,8 @@ async function verifyPass(uri, options) {
 
 module.exports = {
   plonk: { setup, prove, fullProve, verify, verifyBatch, exportSolidityCallData },
-  zKey: { exportVerificationKey, exportSolidityVerifier },
+  zKey: { exportVerificationKey, exportSolidityVerifier, check: zKeyCheck },
+  powersOfTau: { check: powersOfTauCheck },
   nzcp: Object.assign({}, nzcpHost, { witness: nzcpWitness, verifyPass, verifyPasses, p256Verify, decodePasses }),
   wtns: { calculate: wtnsCalculate, remapProgram, check: wtnsCheck },
   r1cs: { info: r1csInfo },

@@ -53,6 +53,8 @@ EXPORTED_SYMBOLS = [
     "nzcb_p256_key_create", "nzcb_p256_verify", "nzcb_p256_key_destroy", "nzcb_engine_p256_key_create",
     "nzcb_debug_p256_field", "nzcb_debug_p256_mul2", "nzcb_debug_p256_timings",
     "nzcb_nzcp_pass_layout", "nzcb_nzcp_decode", "nzcb_nzcp_decode_dev", "nzcb_debug_nzcp_decode_timings",
+    "nzcb_ptau_check", "nzcb_ptau_check_file", "nzcb_zkey_check", "nzcb_zkey_check_file", "nzcb_engine_srs_check",
+    "nzcb_debug_key_check_timings",
 ]
 
 NZCB_FAULT_QUOTIENT = 1  # include/nzcb_internal.h
@@ -69,6 +71,10 @@ PASS_STATUS_NAMES = ("OK", "LENGTH", "PREFIX", "BASE32", "TRUNCATED", "CBOR", "N
                      "CLAIMS")  # include/nzcb.h NZCB_PASS_*
 PASS_HAS_ALG, PASS_HAS_KID, PASS_HAS_ISS, PASS_HAS_NBF, PASS_HAS_EXP, PASS_HAS_CTI, PASS_HAS_SIG = (
     1, 2, 4, 8, 16, 32, 64)  # include/nzcb.h NZCB_PASS_HAS_*
+KEY_HOST = -1  # include/nzcb.h NZCB_KEY_HOST: the key material check on the host
+KEY_STATUS_NAMES = ("OK", "G2", "RANGE", "CURVE", "GENERATOR", "SEQUENCE", "COSETS", "NONCANONICAL", "LAGRANGE",
+                    "EVALS", "COMMIT")  # include/nzcb.h NZCB_KEY_*
+KEY_PARTS = ("Qm", "Ql", "Qr", "Qo", "Qc", "S1", "S2", "S3")  # nzcb_zkey_check's parts 0..7, then L0, L1, ...
 P256_OPS = {"add": 0, "sub": 1, "mul": 2, "sqr": 3, "inv": 4}  # include/nzcb_internal.h NZCB_P256_OP_*
 
 
@@ -160,6 +166,11 @@ LOG_FN = ctypes.CFUNCTYPE(None, c_void_p, ctypes.c_char_p)
 MSM_SEND_FN = ctypes.CFUNCTYPE(c_int, c_void_p, c_int, c_void_p, c_size_t)
 MSM_GATHER_FN = ctypes.CFUNCTYPE(c_int, c_void_p, c_int, POINTER(c_uint8), POINTER(c_uint8))
 MSM_LAGRANGE = 0x100   # include/nzcb.h NZCB_MSM_LAGRANGE: the slot's commitment is over the Lagrange basis
+
+class KeyFinding(ctypes.Structure):  # include/nzcb.h nzcb_key_finding
+    _fields_ = [("status", ctypes.c_int32), ("pairing_checks", c_uint32), ("index", ctypes.c_uint64),
+                ("n_bad", ctypes.c_uint64), ("checked", ctypes.c_uint64)]
+
 
 _lib = None
 
@@ -303,6 +314,17 @@ def load(path: str | None = None):
         "nzcb_nzcp_decode_dev": (c_int, [c_int, c_void_p, c_void_p, c_int, POINTER(NzcpParams), c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_size_t, c_void_p, POINTER(_Err)]),
         "nzcb_debug_nzcp_decode_timings": (c_int, [POINTER(c_double), c_int]),
+        "nzcb_ptau_check": (c_int, [c_void_p, c_size_t, ctypes.c_uint64, c_int, u8p, POINTER(KeyFinding),
+                                    POINTER(_Err)]),
+        "nzcb_ptau_check_file": (c_int, [ctypes.c_char_p, ctypes.c_uint64, c_int, u8p, POINTER(KeyFinding),
+                                         POINTER(_Err)]),
+        "nzcb_zkey_check": (c_int, [c_void_p, c_size_t, c_int, u8p, POINTER(c_int), POINTER(KeyFinding),
+                                    POINTER(KeyFinding), c_uint32, POINTER(c_uint32), POINTER(_Err)]),
+        "nzcb_zkey_check_file": (c_int, [ctypes.c_char_p, c_int, u8p, POINTER(c_int), POINTER(KeyFinding),
+                                         POINTER(KeyFinding), c_uint32, POINTER(c_uint32), POINTER(_Err)]),
+        "nzcb_engine_srs_check": (c_int, [c_int, c_void_p, ctypes.c_uint64, u8p, u8p, c_uint32, POINTER(KeyFinding),
+                                          u8p, POINTER(_Err)]),
+        "nzcb_debug_key_check_timings": (c_int, [POINTER(c_double), c_int]),
     }
     lib.missing_symbols = []
     for name, (res, args) in sigs.items():
@@ -684,6 +706,26 @@ class Engine:
         """Milliseconds of this thread's last verify_batch (nzcb_debug_verify_batch_timings)."""
         ms = (c_double * 6)()
         k = load().nzcb_debug_verify_batch_timings(ms, 6)
+        return list(ms)[:k]
+
+    @staticmethod
+    def srs_check(points: bytes, g2: bytes, device: int = 0, seed: bytes | None = None, chunk_points: int = 0):
+        """nzcb_engine_srs_check: (finding, L || R of the whole range, 128 B) for m x 64-byte LEM points
+        against the 128-byte G2 point; device = KEY_HOST runs the host path."""
+        assert len(points) % 64 == 0 and len(g2) == 128 and (seed is None or len(seed) == 32)
+        f = KeyFinding()
+        lr = _out(128)
+        err = _Err()
+        _check(load().nzcb_engine_srs_check(device, ctypes.cast(_buf(points), c_void_p), len(points) // 64, _buf(g2),
+                                            _buf(seed) if seed else None, chunk_points, ctypes.byref(f), lr,
+                                            ctypes.byref(err)), err)
+        return _finding_dict(f), bytes(lr)
+
+    @staticmethod
+    def key_check_timings() -> list:
+        """Milliseconds of this thread's last key check (nzcb_debug_key_check_timings)."""
+        ms = (c_double * 9)()
+        k = load().nzcb_debug_key_check_timings(ms, 9)
         return list(ms)[:k]
 
 
@@ -1696,6 +1738,84 @@ def _take(ptr, size: int) -> bytes:
     """bytes of a library buffer (ctypes.string_at takes an int size, < 2 GiB)."""
     addr = ctypes.cast(ptr, c_void_p).value if not isinstance(ptr, int) else ptr
     return bytes((c_uint8 * size).from_address(addr)) if size else b""
+
+
+def _finding_dict(f: KeyFinding) -> dict:
+    return {"status": KEY_STATUS_NAMES[f.status], "pairing_checks": f.pairing_checks, "index": f.index,
+            "n_bad": f.n_bad, "checked": f.checked}
+
+
+def _host_view(data):
+    """(pointer, length, keep-alive) of key material in host memory; bytes and bytearrays are not
+    copied (a zkey can be several GB)."""
+    if isinstance(data, bytearray):
+        keep = (c_uint8 * len(data)).from_buffer(data)
+        return ctypes.cast(keep, c_void_p), len(data), keep
+    if not isinstance(data, bytes):
+        data = bytes(data)
+    return ctypes.cast(ctypes.c_char_p(data), c_void_p), len(data), data
+
+
+def ptau_check(ptau_or_path, count: int = 0, device: int = 0, seed: bytes | None = None) -> dict:
+    """Examine a powers-of-tau file (bytes, or a path, which is memory-mapped) on GPU `device`
+    (KEY_HOST: on the host) before a setup uses it (include/nzcb.h nzcb_ptau_check): every tauG1
+    point on the curve, P_0 the generator, and P_i = tau P_(i-1) against the file's [tau]G2 by
+    one pairing check under random weights. count = 0 checks every point the header promises,
+    otherwise the first `count` (a circuit of domain 2^p uses 2^p + 6). Returns the finding:
+    status ("OK", "G2", "RANGE", "CURVE", "GENERATOR", "SEQUENCE"), index, n_bad, checked,
+    pairing_checks. A malformed file raises NzcbError. seed: 32 bytes, for reproducible tests only."""
+    if seed is not None and len(seed) != 32:
+        raise ValueError("ptau_check: the seed is 32 bytes")
+    f = KeyFinding()
+    err = _Err()
+    sd = _buf(seed) if seed else None
+    if isinstance(ptau_or_path, (str, os.PathLike)):
+        rc = load().nzcb_ptau_check_file(os.fsencode(ptau_or_path), count, device, sd, ctypes.byref(f),
+                                         ctypes.byref(err))
+    else:
+        ptr, n, keep = _host_view(ptau_or_path)
+        rc = load().nzcb_ptau_check(ptr, n, count, device, sd, ctypes.byref(f), ctypes.byref(err))
+        del keep
+    _check(rc, err)
+    return _finding_dict(f)
+
+
+def zkey_check(zkey_or_path, device: int = 0, seed: bytes | None = None) -> dict:
+    """Examine a PLONK zkey (bytes, or a path, which is memory-mapped) on GPU `device` (KEY_HOST:
+    on the host) before a context loads it (include/nzcb.h nzcb_zkey_check). Returns
+    {"ok": bool, "header": finding of k1, k2 (COSETS), "srs": finding of the key's PTau against
+    X_2, "parts": {"Qm": finding, ..., "S3": ..., "L0": ...}}; a part's status is "OK",
+    "NONCANONICAL", "LAGRANGE", "EVALS" or "COMMIT" and carries commit_checked. Whether the key
+    belongs to your circuit is not examined: that needs the r1cs."""
+    if seed is not None and len(seed) != 32:
+        raise ValueError("zkey_check: the seed is 32 bytes")
+    lib = load()
+    ok = c_int(0)
+    hdr = (KeyFinding * 2)()
+    n_parts = c_uint32(0)
+    err = _Err()
+    sd = _buf(seed) if seed else None
+    cap = 64
+    while True:
+        parts = (KeyFinding * cap)()
+        if isinstance(zkey_or_path, (str, os.PathLike)):
+            rc = lib.nzcb_zkey_check_file(os.fsencode(zkey_or_path), device, sd, ctypes.byref(ok), hdr, parts, cap,
+                                          ctypes.byref(n_parts), ctypes.byref(err))
+        else:
+            ptr, n, keep = _host_view(zkey_or_path)
+            rc = lib.nzcb_zkey_check(ptr, n, device, sd, ctypes.byref(ok), hdr, parts, cap, ctypes.byref(n_parts),
+                                     ctypes.byref(err))
+            del keep
+        _check(rc, err)
+        if n_parts.value <= cap:
+            break
+        cap = n_parts.value
+    out = {}
+    for k in range(n_parts.value):
+        d = _finding_dict(parts[k])
+        d["commit_checked"] = bool(d.pop("pairing_checks"))
+        out[KEY_PARTS[k] if k < 8 else f"L{k - 8}"] = d
+    return {"ok": bool(ok.value), "header": _finding_dict(hdr[0]), "srs": _finding_dict(hdr[1]), "parts": out}
 
 
 def ptau_synth(power: int, tau: int, device: int = 0) -> bytes:
