@@ -613,6 +613,58 @@ int nzcb_zkey_check(const uint8_t* zkey, size_t len, int device, const uint8_t* 
 int nzcb_zkey_check_file(const char* path, int device, const uint8_t* seed, int* ok, nzcb_key_finding* header_srs,
                          nzcb_key_finding* parts, uint32_t parts_cap, uint32_t* n_parts, nzcb_err* err);
 
+/* ---- Powers of tau: new, contribute, prepare phase 2 (csrc/ptau_ops.h, csrc/ptau_ops.hip) ---- */
+/* The three steps of snarkjs's `phase1` recipe (`powersoftau new`, `contribute`, `prepare phase2`)
+ * for bn128 and 1 <= power <= 24 (NZCB_ERR_ARG outside that). Points are LEM affine as in the
+ * other sections this library reads; the point at infinity is all zero bytes. A file holds
+ *   1 header (n8 = 32, q, power, ceremonyPower), 2 tauG1 (2^(power+1) - 1 points), 3 tauG2
+ *   (2^power), 4 alphaTauG1 (2^power), 5 betaTauG1 (2^power), 6 betaG2 (1), 7 contributions,
+ * and a prepared file also 12, 13, 14, 15, the Lagrange forms of 2, 3, 4, 5.
+ * Each operation has a buffer form (result malloc'ed, release with nzcb_free) and a _file form
+ * that maps the input and writes the output path itself (a prepared power-21 file is 2.25 GiB);
+ * the output path must not be the input file. device = NZCB_PTAU_HOST runs the same steps on the
+ * host (no speed target); the bytes are identical. A call owns its stream and buffers, needs no
+ * nzcb_ctx and may run while a context proves on the same device.
+ *
+ * nzcb_ptau_new: sections 1-7 with every point its group's generator and section 7 = u32 0.
+ * Host only.
+ *
+ * nzcb_ptau_contribute: with `old` the input's point at index i, the output holds
+ *   tauG1[i] = tau^i old, tauG2[i] = tau^i old, alphaTauG1[i] = alpha tau^i old,
+ *   betaTauG1[i] = beta tau^i old, betaG2 = beta old;
+ * sections 1 and 7 are copied, sections 12-15 and unknown sections are dropped (they would be
+ * stale). secrets: 96 B, tau || alpha || beta, 32-byte LE each, in [1, r) (NZCB_ERR_ARG
+ * otherwise), or NULL: 96 bytes from the OS CSPRNG, each secret keccak256(random || entropy ||
+ * k) mod r for k = 0, 1, 2 (k one byte, the digest read as a big-endian integer; a zero result
+ * is redrawn); entropy may be NULL with entropy_len = 0. Caller-given secrets are FOR
+ * REPRODUCIBLE TESTS ONLY: whoever knows them knows the trapdoor of the output. The secrets
+ * are wiped from host and device memory before the call returns and are never logged or
+ * returned. Before any arithmetic every input point is tested on the GPU: a stored coordinate
+ * below q and the point on its curve (G1: y^2 = x^3 + 3; G2: the twist y^2 = x^3 + 3 / (9 + u));
+ * (0, 0) fails. The failure is NZCB_ERR_FORMAT "ptau: section <id> point <lowest bad index> ...".
+ * Membership of a G2 point in the subgroup of order r is NOT tested per point.
+ * NO CONTRIBUTION RECORD IS WRITTEN: no blake2b challenge chain and no proofs of knowledge, so
+ * `snarkjs powersoftau verify` does not accept the output. The use is re-randomising a file for
+ * yourself so that nobody knows its trapdoor, not an audited multi-party ceremony.
+ *
+ * nzcb_ptau_prepare_phase2: copies sections 1-7 and appends 12-15. For a source section with
+ * points P_i and a level p, n = 2^p: out_p[k] = sum_{i<n} (1/n) w_n^(-ik) P_i in natural order,
+ * w_n the root of unity the prover's transforms use. A section is its levels p = 0..power back
+ * to back (level 0 is P_0); section 12 also carries level power + 1 over the 2^(power+1) - 1
+ * tauG1 points followed by the point at infinity. (0, 0) in the input is the point at infinity;
+ * the input's points are not tested. */
+#define NZCB_PTAU_HOST (-1)
+int nzcb_ptau_new(int power, uint8_t** ptau_out, size_t* ptau_len, nzcb_err* err);
+int nzcb_ptau_new_file(int power, const char* out_path, nzcb_err* err);
+int nzcb_ptau_contribute(const uint8_t* ptau, size_t len, const uint8_t* secrets /* 96 B or NULL */,
+                         const uint8_t* entropy, size_t entropy_len, int device /* >= 0, or NZCB_PTAU_HOST */,
+                         uint8_t** ptau_out, size_t* ptau_len, nzcb_err* err);
+int nzcb_ptau_contribute_file(const char* in_path, const char* out_path, const uint8_t* secrets,
+                              const uint8_t* entropy, size_t entropy_len, int device, nzcb_err* err);
+int nzcb_ptau_prepare_phase2(const uint8_t* ptau, size_t len, int device, uint8_t** ptau_out, size_t* ptau_len,
+                             nzcb_err* err);
+int nzcb_ptau_prepare_phase2_file(const char* in_path, const char* out_path, int device, nzcb_err* err);
+
 /* ---- HBM buffers (witnesses for nzcb_prove_device / nzcb_prove_batch on device) ---- */
 void* nzcb_dev_alloc(size_t bytes);
 /* The same on `device`; the calling thread's current device is left as it was (the N-API

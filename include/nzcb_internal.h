@@ -235,6 +235,18 @@ int nzcb_engine_srs_check(int device, const uint8_t* points, uint64_t m, const u
  * (cap <= 9). */
 int nzcb_debug_key_check_timings(double* ms, int cap);
 
+/* ---- Powers of tau operations (csrc/ptau_ops.h, csrc/ptau_ops.hip) ----------------------- */
+/* Milliseconds of the calling thread's last nzcb_ptau_contribute or nzcb_ptau_prepare_phase2:
+ * [0] the kernels (HIP events; 0 on the host path), [1] the call's wall time. Returns the number
+ * of values written (cap <= 2). */
+int nzcb_debug_ptau_timings(double* ms, int cap);
+/* The device path of nzcb_ptau_prepare_phase2 transforms the levels 0..batch_top of a section in
+ * one run (one launch per stage for all of them) and every larger level in a run of its own, so
+ * its work space is that of the top level. Sets batch_top for the calls that follow (the
+ * library's constant is 16; level < 0 restores it) and returns the previous value. The bytes do
+ * not depend on it. Not thread-safe: for tests. */
+int nzcb_debug_ptau_batch_top(int level);
+
 #ifdef __cplusplus
 }
 #endif

@@ -928,6 +928,80 @@ napi_value KeyCheck(napi_env env, napi_callback_info info) {
   return promise;
 }
 
+// one powersOfTau.newAccumulator / contribute / preparePhase2 call (nzcb_ptau_new_file,
+// nzcb_ptau_contribute_file, nzcb_ptau_prepare_phase2_file) on a worker thread (async work);
+// the promise is settled on the main thread. Files are mapped and written by the library.
+struct PtauOpWork {
+  napi_deferred deferred = nullptr;
+  napi_async_work work = nullptr;
+  int kind = 0;  // 0 new, 1 contribute, 2 prepare phase 2
+  int power = 0, device = 0;
+  std::string in_path, out_path, entropy;
+  int rc = 0;
+  nzcb_err err{};
+};
+
+void ptau_op_execute(napi_env, void* data) {
+  PtauOpWork* w = static_cast<PtauOpWork*>(data);
+  if (w->kind == 0)
+    w->rc = nzcb_ptau_new_file(w->power, w->out_path.c_str(), &w->err);
+  else if (w->kind == 1)
+    w->rc = nzcb_ptau_contribute_file(w->in_path.c_str(), w->out_path.c_str(), nullptr,
+                                      reinterpret_cast<const uint8_t*>(w->entropy.data()), w->entropy.size(),
+                                      w->device, &w->err);
+  else
+    w->rc = nzcb_ptau_prepare_phase2_file(w->in_path.c_str(), w->out_path.c_str(), w->device, &w->err);
+}
+
+void ptau_op_complete(napi_env env, napi_status status, void* data) {
+  PtauOpWork* w = static_cast<PtauOpWork*>(data);
+  if (status != napi_ok || w->rc != 0) {
+    napi_reject_deferred(env, w->deferred,
+                         make_error(env, w->rc ? w->err.code : NZCB_ERR_INTERNAL,
+                                    w->rc ? w->err.msg : "ptauOp: the work was cancelled"));
+  } else {
+    napi_value undef;
+    napi_get_undefined(env, &undef);
+    napi_resolve_deferred(env, w->deferred, undef);
+  }
+  napi_delete_async_work(env, w->work);
+  delete w;
+}
+
+// ptauOp(kind: 0 = new | 1 = contribute | 2 = prepare phase 2, in: string (file name; ignored for
+//   new), out: string (file name), power: number (new only), entropy: string, device: number)
+//   -> Promise<undefined>. The secrets of a contribution are drawn inside the library.
+napi_value PtauOp(napi_env env, napi_callback_info info) {
+  size_t argc = 6;
+  napi_value argv[6];
+  CHECK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  PtauOpWork* w = new PtauOpWork();
+  int32_t kind = -1, power = 0, device = 0;
+  bool ok = argc >= 3 && napi_get_value_int32(env, argv[0], &kind) == napi_ok && kind >= 0 && kind <= 2 &&
+            (kind == 0 || str_arg(env, argv[1], &w->in_path)) && str_arg(env, argv[2], &w->out_path);
+  if (ok && argc > 3) napi_get_value_int32(env, argv[3], &power);
+  if (ok && argc > 4) (void)str_arg(env, argv[4], &w->entropy);
+  if (ok && argc > 5) napi_get_value_int32(env, argv[5], &device);
+  if (!ok) {
+    delete w;
+    napi_throw_type_error(env, nullptr, "ptauOp(kind: 0 | 1 | 2, in: string, out: string, power?, entropy?, device?)");
+    return nullptr;
+  }
+  w->kind = kind;
+  w->power = power;
+  w->device = device;
+  napi_value promise, name;
+  if (napi_create_promise(env, &w->deferred, &promise) != napi_ok ||
+      napi_create_string_utf8(env, "nzcb.ptauOp", NAPI_AUTO_LENGTH, &name) != napi_ok ||
+      napi_create_async_work(env, nullptr, name, ptau_op_execute, ptau_op_complete, w, &w->work) != napi_ok ||
+      napi_queue_async_work(env, w->work) != napi_ok) {
+    delete w;
+    napi_throw_error(env, nullptr, "nzcb addon: N-API call failed");
+    return nullptr;
+  }
+  return promise;
+}
+
 // one p256Verify call: the key's tables built (nzcb_p256_key_create), the batch verified
 // (nzcb_p256_verify) and the key released, on a worker thread (async work); the promise is
 // settled on the main thread. The inputs are copied.
@@ -1312,6 +1386,7 @@ napi_value Init(napi_env env, napi_value exports) {
       {"releaseContext", nullptr, ReleaseContext, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"wtnsCheck", nullptr, WtnsCheck, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"keyCheck", nullptr, KeyCheck, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"ptauOp", nullptr, PtauOp, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"r1csInfo", nullptr, R1csInfo, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"p256Verify", nullptr, P256Verify, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"nzcpDecode", nullptr, NzcpDecode, nullptr, nullptr, nullptr, napi_default, nullptr},

@@ -26,6 +26,12 @@
 //     (the issuer's P-256 key as base64url JWK coordinates, default the specification's example
 //     key; prints "OK", "INVALID SIGNATURE" or the reason per pass and exits 0 only if all are
 //     valid; NZCB_DEVICE=-1 verifies on the host)
+// and the `phase1` recipe of snarkjs (Makefile), with only the program name changed:
+//   node cli.js powersoftau new bn128 <power> <pot_0000.ptau> -v
+//   node cli.js powersoftau contribute <pot_0000.ptau> <pot_0001.ptau> --name="First contribution" -v
+//   node cli.js powersoftau prepare phase2 <pot_0001.ptau> <pot_final.ptau> -v
+//     (contribute draws its secrets from the OS, mixed with -e=<entropy>; it writes NO contribution
+//     record, so `snarkjs powersoftau verify` does not accept the file; NZCB_DEVICE=-1 runs on the host)
 // Output JSON is written like snarkjs's CLI (stringifyBigInts, 1-space indent).
 const fs = require('fs');
 const nz = require('./index.js');
@@ -42,7 +48,10 @@ function usage() {
                 '       cli.js powersoftau check <ptau> [power]\n' +
                 '       cli.js zkey check <zkey>\n' +
                 '       cli.js r1cs info <r1cs>\n' +
-                '       cli.js nzcp verify <file with one pass URI per line> [example | <x> <y>]');
+                '       cli.js nzcp verify <file with one pass URI per line> [example | <x> <y>]\n' +
+                '       cli.js powersoftau new bn128 <power> <new.ptau> [-v]\n' +
+                '       cli.js powersoftau contribute <old.ptau> <new.ptau> [--name=<text>] [-e=<entropy>] [-v]\n' +
+                '       cli.js powersoftau prepare phase2 <old.ptau> <new.ptau> [-v]');
   process.exit(1);
 }
 
@@ -76,7 +85,38 @@ async function keyCheck(argv) {
   process.exit(f.status === 'OK' ? 0 : 1);
 }
 
+// powersoftau new | contribute | prepare phase2 with snarkjs's options: -v (log to the console),
+// --name=<text> / -n=<text> and --entropy=<text> / -e=<text> (contribute)
+async function phase1(argv) {
+  const opts = { name: '', entropy: '' };
+  const args = [];
+  let verbose = false;
+  for (const a of argv.slice(1)) {
+    const m = /^(--name|-n|--entropy|-e)=(.*)$/s.exec(a);
+    if (m) opts[m[1] === '--name' || m[1] === '-n' ? 'name' : 'entropy'] = m[2];
+    else if (a === '-v' || a === '--verbose') verbose = true;
+    else if (a.startsWith('-')) usage();
+    else args.push(a);
+  }
+  const logger = verbose ? { info: (m) => console.log(m) } : null;
+  if (args[0] === 'new' && args.length === 4) {
+    const power = Number(args[2]);
+    if (!Number.isInteger(power)) usage();
+    return nz.powersOfTau.newAccumulator(args[1], power, args[3], logger);
+  }
+  if (args[0] === 'contribute' && args.length === 3) {
+    // the CLI always says what the file is not, -v or not
+    const say = { info: (m) => console.log(m) };
+    return nz.powersOfTau.contribute(args[1], args[2], opts.name, opts.entropy, say);
+  }
+  if (args[0] === 'prepare' && args[1] === 'phase2' && args.length === 4) {
+    return nz.powersOfTau.preparePhase2(args[2], args[3], logger);
+  }
+  usage();
+}
+
 async function main(argv) {
+  if (argv[0] === 'powersoftau' && (argv[1] === 'new' || argv[1] === 'contribute' || argv[1] === 'prepare')) return phase1(argv);
   if (argv[0] === 'zkey' && argv[1] === 'check' && argv.length === 3) return keyCheck(argv);
   if (argv[0] === 'powersoftau' && argv[1] === 'check' && (argv.length === 3 || argv.length === 4)) return keyCheck(argv);
   if (argv[0] === 'zkey') return zkeyExport(argv);

@@ -522,6 +522,54 @@ async function powersOfTauCheck(ptau, logger, options) {
   if (info) info(findingLine('tauG1', f));
   return f;
 }
+// snarkjs's `phase1` recipe (include/nzcb.h nzcb_ptau_new, nzcb_ptau_contribute,
+// nzcb_ptau_prepare_phase2), with snarkjs's names and argument order, file names only; each runs
+// on a worker thread. NZCB_DEVICE selects the GPU (-1 = on the host) when options.device is not
+// given.
+// powersOfTau.newAccumulator(curve, power, fileName, logger): curve is "bn128" or an object whose
+//   name is that.
+// powersOfTau.contribute(oldPtauFileName, newPtauFileName, name, entropy, logger): multiplies
+//   fresh secrets from the OS CSPRNG, mixed with `entropy`, into every section. NO contribution
+//   record is written (`name` is only logged), so `snarkjs powersoftau verify` does not accept the
+//   result: this re-randomises a file for yourself, it is not an audited ceremony.
+// powersOfTau.preparePhase2(oldPtauFileName, newPtauFileName, logger): appends the Lagrange
+//   sections 12-15 that snarkjs's setups read.
+function ptauDevice(options) {
+  if (options && options.device !== undefined) return options.device;
+  return process.env.NZCB_DEVICE === undefined ? 0 : Number(process.env.NZCB_DEVICE);
+}
+function ptauLog(logger) {
+  return logger && typeof logger.info === 'function' ? (m) => logger.info(m) : loggerFn(logger);
+}
+async function newAccumulator(curve, power, fileName, logger) {
+  const curveName = curve && typeof curve === 'object' ? curve.name : curve;
+  if (String(curveName).toLowerCase() !== 'bn128') throw new Error(`Curve not supported: ${curveName}`);
+  if (typeof fileName !== 'string') throw new TypeError('newAccumulator: fileName must be a string');
+  await addon.ptauOp(0, '', fileName, Number(power), '', 0);
+  const log = ptauLog(logger);
+  if (log) log(`powersoftau new: bn128, power ${power}, no contributions`);
+}
+async function contribute(oldPtauFileName, newPtauFileName, name, entropy, logger, options) {
+  if (typeof oldPtauFileName !== 'string' || typeof newPtauFileName !== 'string') {
+    throw new TypeError('contribute: file names must be strings');
+  }
+  await addon.ptauOp(1, oldPtauFileName, newPtauFileName, 0, entropy === undefined || entropy === null ? '' : String(entropy),
+                     ptauDevice(options));
+  const log = ptauLog(logger);
+  if (log) {
+    log(`powersoftau contribute: "${name || ''}" applied; NO contribution record written ` +
+        '(snarkjs powersoftau verify will not accept this file)');
+  }
+}
+async function preparePhase2(oldPtauFileName, newPtauFileName, logger, options) {
+  if (typeof oldPtauFileName !== 'string' || typeof newPtauFileName !== 'string') {
+    throw new TypeError('preparePhase2: file names must be strings');
+  }
+  await addon.ptauOp(2, oldPtauFileName, newPtauFileName, 0, '', ptauDevice(options));
+  const log = ptauLog(logger);
+  if (log) log('powersoftau prepare phase2: sections 12-15 written');
+}
+
 // zKey.check(zkey, logger, {device}): the key's cosets, its PTau against X_2, and per polynomial
 // the canonical values, the evaluations against the coefficients and the header's commitment.
 // Resolves to {ok, header, srs, parts: {Qm, ..., S3, L0, ...}} and logs one line per finding.
@@ -819,7 +867,7 @@ async function verifyPass(uri, options) {
 module.exports = {
   plonk: { setup, prove, fullProve, verify, verifyBatch, exportSolidityCallData },
   zKey: { exportVerificationKey, exportSolidityVerifier, check: zKeyCheck },
-  powersOfTau: { check: powersOfTauCheck },
+  powersOfTau: { check: powersOfTauCheck, newAccumulator, contribute, preparePhase2 },
   nzcp: Object.assign({}, nzcpHost, { witness: nzcpWitness, verifyPass, verifyPasses, p256Verify, decodePasses }),
   wtns: { calculate: wtnsCalculate, remapProgram, check: wtnsCheck },
   r1cs: { info: r1csInfo },

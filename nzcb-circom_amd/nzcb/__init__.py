@@ -55,6 +55,9 @@ EXPORTED_SYMBOLS = [
     "nzcb_nzcp_pass_layout", "nzcb_nzcp_decode", "nzcb_nzcp_decode_dev", "nzcb_debug_nzcp_decode_timings",
     "nzcb_ptau_check", "nzcb_ptau_check_file", "nzcb_zkey_check", "nzcb_zkey_check_file", "nzcb_engine_srs_check",
     "nzcb_debug_key_check_timings",
+    "nzcb_ptau_new", "nzcb_ptau_new_file", "nzcb_ptau_contribute", "nzcb_ptau_contribute_file",
+    "nzcb_ptau_prepare_phase2", "nzcb_ptau_prepare_phase2_file", "nzcb_debug_ptau_timings",
+    "nzcb_debug_ptau_batch_top",
 ]
 
 NZCB_FAULT_QUOTIENT = 1  # include/nzcb_internal.h
@@ -72,6 +75,7 @@ PASS_STATUS_NAMES = ("OK", "LENGTH", "PREFIX", "BASE32", "TRUNCATED", "CBOR", "N
 PASS_HAS_ALG, PASS_HAS_KID, PASS_HAS_ISS, PASS_HAS_NBF, PASS_HAS_EXP, PASS_HAS_CTI, PASS_HAS_SIG = (
     1, 2, 4, 8, 16, 32, 64)  # include/nzcb.h NZCB_PASS_HAS_*
 KEY_HOST = -1  # include/nzcb.h NZCB_KEY_HOST: the key material check on the host
+PTAU_HOST = -1  # include/nzcb.h NZCB_PTAU_HOST: the powers-of-tau operations on the host
 KEY_STATUS_NAMES = ("OK", "G2", "RANGE", "CURVE", "GENERATOR", "SEQUENCE", "COSETS", "NONCANONICAL", "LAGRANGE",
                     "EVALS", "COMMIT")  # include/nzcb.h NZCB_KEY_*
 KEY_PARTS = ("Qm", "Ql", "Qr", "Qo", "Qc", "S1", "S2", "S3")  # nzcb_zkey_check's parts 0..7, then L0, L1, ...
@@ -325,6 +329,17 @@ def load(path: str | None = None):
         "nzcb_engine_srs_check": (c_int, [c_int, c_void_p, ctypes.c_uint64, u8p, u8p, c_uint32, POINTER(KeyFinding),
                                           u8p, POINTER(_Err)]),
         "nzcb_debug_key_check_timings": (c_int, [POINTER(c_double), c_int]),
+        "nzcb_ptau_new": (c_int, [c_int, POINTER(POINTER(c_uint8)), POINTER(c_size_t), POINTER(_Err)]),
+        "nzcb_ptau_new_file": (c_int, [c_int, ctypes.c_char_p, POINTER(_Err)]),
+        "nzcb_ptau_contribute": (c_int, [c_void_p, c_size_t, u8p, ctypes.c_char_p, c_size_t, c_int,
+                                         POINTER(POINTER(c_uint8)), POINTER(c_size_t), POINTER(_Err)]),
+        "nzcb_ptau_contribute_file": (c_int, [ctypes.c_char_p, ctypes.c_char_p, u8p, ctypes.c_char_p, c_size_t,
+                                              c_int, POINTER(_Err)]),
+        "nzcb_ptau_prepare_phase2": (c_int, [c_void_p, c_size_t, c_int, POINTER(POINTER(c_uint8)),
+                                             POINTER(c_size_t), POINTER(_Err)]),
+        "nzcb_ptau_prepare_phase2_file": (c_int, [ctypes.c_char_p, ctypes.c_char_p, c_int, POINTER(_Err)]),
+        "nzcb_debug_ptau_timings": (c_int, [POINTER(c_double), c_int]),
+        "nzcb_debug_ptau_batch_top": (c_int, [c_int]),
     }
     lib.missing_symbols = []
     for name, (res, args) in sigs.items():
@@ -1831,6 +1846,113 @@ def ptau_synth(power: int, tau: int, device: int = 0) -> bytes:
         return _take(pp, pl.value)
     finally:
         lib.nzcb_free(pp)
+
+
+def _take_ptau(lib, pp, pl) -> bytes:
+    try:
+        return _take(pp, pl.value)
+    finally:
+        lib.nzcb_free(pp)
+
+
+def _is_path(x) -> bool:
+    return isinstance(x, (str, os.PathLike))
+
+
+def ptau_new(power: int, out_path=None):
+    """snarkjs ``powersoftau new bn128 <power>``: a powers-of-tau file (sections 1-7) whose every
+    point is its group's generator and that holds no contribution (include/nzcb.h nzcb_ptau_new;
+    host only). Returns the bytes, or writes `out_path` and returns it."""
+    lib = load()
+    err = _Err()
+    if out_path is not None:
+        _check(lib.nzcb_ptau_new_file(power, os.fsencode(out_path), ctypes.byref(err)), err)
+        return out_path
+    pp, pl = POINTER(c_uint8)(), c_size_t()
+    _check(lib.nzcb_ptau_new(power, ctypes.byref(pp), ctypes.byref(pl), ctypes.byref(err)), err)
+    return _take_ptau(lib, pp, pl)
+
+
+def ptau_contribute(ptau_or_path, out_path=None, secrets=None, entropy=None, device: int = 0):
+    """Multiply your own secret into a powers-of-tau file on GPU `device` (PTAU_HOST: on the host):
+    tauG1[i], tauG2[i] by tau^i, alphaTauG1[i] by alpha tau^i, betaTauG1[i] by beta tau^i, betaG2
+    by beta (include/nzcb.h nzcb_ptau_contribute). secrets = None draws tau, alpha and beta from
+    the OS CSPRNG, mixed with the optional `entropy` (str or bytes); a (tau, alpha, beta) tuple of
+    integers in [1, r) is FOR REPRODUCIBLE TESTS ONLY. Every input point is tested first; a bad one
+    raises NzcbError FORMAT naming its section and index. NO contribution record is written:
+    ``snarkjs powersoftau verify`` does not accept the output. The input is bytes, or a path
+    (memory-mapped when `out_path` is given). Returns the bytes, or writes `out_path` and returns it."""
+    lib = load()
+    err = _Err()
+    sec = None
+    if secrets is not None:
+        if len(secrets) != 3:
+            raise ValueError("ptau_contribute: secrets are (tau, alpha, beta)")
+        if any(not 0 <= int(s) < 1 << 256 for s in secrets):
+            raise NzcbError(1, "ptau: a secret is zero or not below r")
+        sec = _buf(b"".join(int(s).to_bytes(32, "little") for s in secrets))
+    ent = entropy.encode() if isinstance(entropy, str) else bytes(entropy or b"")
+    if _is_path(ptau_or_path) and out_path is not None:
+        _check(lib.nzcb_ptau_contribute_file(os.fsencode(ptau_or_path), os.fsencode(out_path), sec, ent, len(ent),
+                                             device, ctypes.byref(err)), err)
+        return out_path
+    if _is_path(ptau_or_path):
+        with open(ptau_or_path, "rb") as f:
+            ptau_or_path = f.read()
+    ptr, n, keep = _host_view(ptau_or_path)
+    pp, pl = POINTER(c_uint8)(), c_size_t()
+    rc = lib.nzcb_ptau_contribute(ptr, n, sec, ent, len(ent), device, ctypes.byref(pp), ctypes.byref(pl),
+                                  ctypes.byref(err))
+    del keep
+    _check(rc, err)
+    out = _take_ptau(lib, pp, pl)
+    if out_path is None:
+        return out
+    with open(out_path, "wb") as f:
+        f.write(out)
+    return out_path
+
+
+def ptau_prepare_phase2(ptau_or_path, out_path=None, device: int = 0):
+    """snarkjs ``powersoftau prepare phase2``: sections 1-7 of the input and the Lagrange sections
+    12-15 that snarkjs's setups read, computed by elliptic-curve inverse transforms on GPU `device`
+    (PTAU_HOST: on the host; include/nzcb.h nzcb_ptau_prepare_phase2). Input and result as for
+    ptau_contribute."""
+    lib = load()
+    err = _Err()
+    if _is_path(ptau_or_path) and out_path is not None:
+        _check(lib.nzcb_ptau_prepare_phase2_file(os.fsencode(ptau_or_path), os.fsencode(out_path), device,
+                                                 ctypes.byref(err)), err)
+        return out_path
+    if _is_path(ptau_or_path):
+        with open(ptau_or_path, "rb") as f:
+            ptau_or_path = f.read()
+    ptr, n, keep = _host_view(ptau_or_path)
+    pp, pl = POINTER(c_uint8)(), c_size_t()
+    rc = lib.nzcb_ptau_prepare_phase2(ptr, n, device, ctypes.byref(pp), ctypes.byref(pl), ctypes.byref(err))
+    del keep
+    _check(rc, err)
+    out = _take_ptau(lib, pp, pl)
+    if out_path is None:
+        return out
+    with open(out_path, "wb") as f:
+        f.write(out)
+    return out_path
+
+
+def ptau_batch_top(level: int) -> int:
+    """Tests: the highest level ptau_prepare_phase2 transforms together with the levels below it
+    on the device (nzcb_debug_ptau_batch_top; < 0 restores the library's constant). Returns the
+    previous value."""
+    return load().nzcb_debug_ptau_batch_top(level)
+
+
+def ptau_timings() -> list:
+    """Milliseconds of this thread's last ptau_contribute or ptau_prepare_phase2: the kernels (HIP
+    events), the call (nzcb_debug_ptau_timings)."""
+    ms = (c_double * 2)()
+    k = load().nzcb_debug_ptau_timings(ms, 2)
+    return list(ms[:k])
 
 
 def synth_setup_raw(power: int, n_public: int = 3, n_inputs: int = 8, seed: int = 0x6E7A6362,
