@@ -665,6 +665,84 @@ int nzcb_ptau_prepare_phase2(const uint8_t* ptau, size_t len, int device, uint8_
                              nzcb_err* err);
 int nzcb_ptau_prepare_phase2_file(const char* in_path, const char* out_path, int device, nzcb_err* err);
 
+/* ---- Groth16 key generation: setup, zkey contribute, verification key (csrc/groth16.h, .hip) ---- */
+/* The first three lines of snarkjs's `phase2` recipe (`groth16 setup`, `zkey contribute`, `zkey
+ * export verificationkey`) for bn128. This is key generation only: there is no Groth16 prover,
+ * verifier or Solidity verifier here, and nzcb_vk_from_zkey, nzcb_ctx_create and nzcb_zkey_check
+ * keep rejecting a Groth16 key ("zkey file is not plonk").
+ *
+ * THE FILE LAYOUT BELOW IS THE SPECIFICATION; PARITY WITH snarkjs 0.4.12 IS UNPINNED (it is
+ * restated from the published format, and snarkjs was not available to compare with).
+ * NO CIRCUIT HASH AND NO CONTRIBUTION RECORDS ARE WRITTEN: section 10 is 64 zero bytes and a
+ * count of 0, there is no blake2b transcript and no proof of knowledge, so `snarkjs zkey verify`
+ * does not accept a key made or contributed to here. The use is making a key for yourself whose
+ * delta nobody knows, not an audited multi-party ceremony.
+ *
+ * nzcb_groth16_setup: an iden3 r1cs over BN254's r (NZCB_ERR_CURVE otherwise) with m constraints,
+ * nVars wires and nPublic = nOutputs + nPubInputs, and a powers-of-tau file with sections 1-7 and
+ * 12-15 as nzcb_ptau_prepare_phase2 writes them (NZCB_ERR_FORMAT "ptau: not prepared for phase 2
+ * (section 12 is missing)" otherwise). cirPower = floor(log2(m + nPublic)) + 1, n = 2^cirPower;
+ * cirPower above the file's power is NZCB_ERR_ARG "circuit too big for this power of tau
+ * ceremony. <m>*2 > 2**<power>". With L12..L15 level cirPower of sections 12-15, T level
+ * cirPower + 1 of section 12 and a, b, c the coefficients of constraint c' at signal s:
+ *   A[s]  = sum a L12[c']  (+ L12[m + s] for s <= nPublic)                       G1, nVars
+ *   B1[s] = sum b L12[c'],  B2[s] = sum b L13[c'] (G2)                           nVars each
+ *   K[s]  = sum a L15[c'] + b L14[c'] + c L12[c']  (+ L15[m + s] for s <= nPublic)
+ *   IC = K[0..nPublic], C = K[nPublic + 1..nVars - 1], H[i] = T[2 i + 1] for i < n,
+ *   alpha1 = section 4 point 0, beta1 = section 5 point 0, beta2 = section 6,
+ *   gamma2 = delta2 = [1]G2, delta1 = [1]G1.
+ * A FRESH KEY HAS delta = gamma = 1: ANYONE CAN FORGE PROOFS UNDER IT UNTIL IT HAS BEEN
+ * CONTRIBUTED TO. A zero coefficient adds nothing to a point but stays in section 4; a wire
+ * listed twice in a linear combination counts twice; an empty sum is the point at infinity.
+ * The file: magic "zkey", version 1, sections 1..10 in order, points LEM affine, infinity all
+ * zero bytes:
+ *   1  u32 1 (groth16)
+ *   2  u32 32, q, u32 32, r, u32 nVars, u32 nPublic, u32 n, alpha1, beta1, beta2, gamma2, delta1, delta2
+ *   3  IC, nPublic + 1 G1
+ *   4  u32 nCoefs, then per entry u32 matrix (0 = A, 1 = B), u32 constraint, u32 signal, 32 B value:
+ *      per constraint in file order A's terms then B's, then nPublic + 1 entries (0, m + s, s, 1).
+ *      A value is coefficient * R^2 mod r, R = 2^256, normal form LE. C's terms are not stored.
+ *   5 A, 6 B1, 7 B2 (G2), 8 C, 9 H
+ *   10 64 zero bytes, u32 0
+ * Every point read is tested on the GPU before any arithmetic (range and curve; all zero bytes
+ * pass as infinity in the Lagrange levels): NZCB_ERR_FORMAT "ptau: section <id> point <lowest bad
+ * index> ...", the index counted within the section. Levels the setup does not read are not
+ * tested. Only the levels used are uploaded.
+ *
+ * nzcb_groth16_contribute: C and H times 1/d, delta1 and delta2 times d; sections 1, 3-7 and 10
+ * are copied. secret: 32 B LE in [1, r) (NZCB_ERR_ARG otherwise), or NULL: d is drawn as
+ * nzcb_ptau_contribute draws tau, keccak256(96 bytes of the OS CSPRNG || entropy || 0) mod r,
+ * redrawn on zero. A caller-given secret is FOR REPRODUCIBLE TESTS ONLY: whoever knows it can
+ * forge proofs. The secret is wiped from host and device memory before the call returns. Every
+ * point of sections 8 and 9 ((0, 0) passes) and the two deltas are tested first: NZCB_ERR_FORMAT
+ * "zkey: section <id> point <lowest bad index> ...". A zkey whose protocol id is not 1:
+ * NZCB_ERR_FORMAT "zkey file is not groth16".
+ *
+ * The _file forms map their inputs (a prepared power-21 ptau is 2.25 GiB) and write the output
+ * path themselves; it must not be an input path. device = NZCB_GROTH16_HOST runs the same steps
+ * on the host with up to 16 threads; the bytes are identical.
+ *
+ * nzcb_groth16_vk_to_json: {"protocol":"groth16","curve":"bn128","nPublic", "vk_alpha_1",
+ * "vk_beta_2","vk_gamma_2","vk_delta_2","IC"} in this order, decimal strings, G1 [x, y, "1"], G2
+ * [[x0, x1], [y0, y1], ["1", "0"]]. snarkjs's vk_alphabeta_12 IS LEFT OUT: its Fq12 layout cannot
+ * be pinned here, and neither snarkjs's verifier nor its Solidity template reads it. Returns 0,
+ * or minus the size needed when cap is short (out may be NULL), or the NZCB_ERR_* code of a file
+ * that is no Groth16 key, with the message in out as far as cap allows. */
+#define NZCB_GROTH16_HOST (-1)
+int nzcb_groth16_setup(const uint8_t* r1cs, size_t r1cs_len, const uint8_t* ptau, size_t ptau_len,
+                       int device /* >= 0, or NZCB_GROTH16_HOST */, uint8_t** zkey_out, size_t* zkey_len,
+                       nzcb_err* err);
+int nzcb_groth16_setup_file(const char* r1cs_path, const char* ptau_path, const char* zkey_path, int device,
+                            nzcb_err* err);
+int nzcb_groth16_contribute(const uint8_t* zkey, size_t len, const uint8_t* secret /* 32 B LE in [1, r), or NULL */,
+                            const uint8_t* entropy, size_t entropy_len, int device, uint8_t** zkey_out,
+                            size_t* zkey_len, nzcb_err* err);
+int nzcb_groth16_contribute_file(const char* in_path, const char* out_path, const uint8_t* secret,
+                                 const uint8_t* entropy, size_t entropy_len, int device, nzcb_err* err);
+int nzcb_groth16_vk_to_json(const uint8_t* zkey, size_t len, char* out, size_t cap);
+/* The same from a file, memory-mapped. */
+int nzcb_groth16_vk_to_json_file(const char* zkey_path, char* out, size_t cap);
+
 /* ---- HBM buffers (witnesses for nzcb_prove_device / nzcb_prove_batch on device) ---- */
 void* nzcb_dev_alloc(size_t bytes);
 /* The same on `device`; the calling thread's current device is left as it was (the N-API

@@ -247,6 +247,33 @@ int nzcb_debug_ptau_timings(double* ms, int cap);
  * not depend on it. Not thread-safe: for tests. */
 int nzcb_debug_ptau_batch_top(int level);
 
+/* ---- Groth16 key generation (csrc/groth16.h, csrc/groth16.hip) --------------------------- */
+/* The kernel family behind nzcb_groth16_setup on bare arrays: out[row] = sum over the row's
+ * terms t in [row_off[row], row_off[row + 1]) of coefs[t] * points[idx[t]], affine LEM, all zero
+ * bytes for the point at infinity. points: n_points LEM affine points, 64 B each (G1) or 128 B
+ * with g2 != 0, IN DEVICE MEMORY on `device` (in host memory with device = NZCB_GROTH16_HOST);
+ * (0, 0) among them is the point at infinity; they are not tested. row_off: n_rows + 1 ascending
+ * offsets from 0; idx below n_points; coefs: 32 B LE normal form below r each (NZCB_ERR_ARG
+ * otherwise). out: n_rows points in host memory. Runs under the current schedule (below). */
+int nzcb_engine_groth16_rows(int device, int g2, const void* points, uint64_t n_points, const uint64_t* row_off,
+                             uint64_t n_rows, const uint32_t* idx, const uint8_t* coefs, uint8_t* out,
+                             nzcb_err* err);
+/* A row is cut into chunks of at most `chunk` terms (and, past a chunk's first term, at most
+ * 4 * chunk expected additions, half a coefficient's bits each), one lane each, and the chunk
+ * partials of a row are folded `fan_in` at a time, level by level. Sets both for the calls that follow (the
+ * library's constants are 32 and 8; <= 0 restores a constant; chunk <= 1024, 2 <= fan_in <= 1024,
+ * NZCB_ERR_ARG otherwise) and writes the previous values (either pointer may be NULL). The bytes
+ * do not depend on them. Not thread-safe: for tests. */
+int nzcb_debug_groth16_schedule(int chunk, int fan_in, int* prev_chunk, int* prev_fan_in);
+/* Of the calling thread's last nzcb_groth16_setup, nzcb_groth16_contribute or
+ * nzcb_engine_groth16_rows. Milliseconds: [0] all kernels (HIP events; 0 on the host path), [1]
+ * the call's wall time, [2] the G1 rows (A, B1 and K in one run: chunks, folds, store), [3] the
+ * G2 rows (B2), [4] the point tests, [5] the scaling of a contribution, [6] the host's reading of
+ * the r1cs, transposed lists and schedule (wall). Counts: [7] terms of A, [8] B1, [9] B2, [10] K
+ * (zero coefficients included), [11] chunks of the G1 run, [12] of the G2 run. Returns the number
+ * of values written (cap <= 13). */
+int nzcb_debug_groth16_timings(double* out, int cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,10 +8,16 @@
 // scalar a lane derives for its index. The header needs no HIP runtime: a host-only program may
 // include it (tests/native/ptau_ops_host.cpp).
 #pragma once
+#include <sys/random.h>
+
+#include <algorithm>
+#include <cerrno>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <thread>
+#include <vector>
 
 #include "capi_guard.h"
 #include "ec.h"
@@ -392,6 +398,93 @@ inline void ptau_new(int power, PtauOut& o, const char* out_path) {
   const uint32_t none = 0;
   std::memcpy(o.section(7, 4), &none, 4);
   o.commit();
+}
+
+// ---------------------------------------------------------------- what the host paths share
+// (ptau_ops.hip and groth16.h)
+inline void wipe(void* p, size_t n) {
+  volatile uint8_t* b = static_cast<volatile uint8_t*>(p);
+  for (size_t i = 0; i < n; i++) b[i] = 0;
+}
+
+struct Tally {  // defective points and the lowest one's key (key_check.h srs_bad_key)
+  uint64_t n_bad = 0, key = kNoBadKey;
+};
+
+// fn(i) for i < n on up to 16 threads of the host
+template <class Fn>
+void parallel_for(uint64_t n, Fn fn) {
+  const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
+  const unsigned nt = (unsigned)std::min<uint64_t>(std::min(16u, hw), n / 4);
+  if (nt <= 1) {
+    for (uint64_t i = 0; i < n; i++) fn(i);
+    return;
+  }
+  std::vector<std::thread> th;
+  for (unsigned t = 0; t < nt; t++) {
+    const uint64_t lo = n * t / nt, hi = n * (t + 1) / nt;
+    th.emplace_back([lo, hi, &fn] {
+      for (uint64_t i = lo; i < hi; i++) fn(i);
+    });
+  }
+  for (auto& t : th) t.join();
+}
+
+inline void os_random(uint8_t* b, size_t len) {
+  size_t got = 0;
+  while (got < len) {
+    const ssize_t k = getrandom(b + got, len - got, 0);
+    if (k < 0) {
+      if (errno == EINTR || errno == EAGAIN) continue;
+      throw Error(NZCB_ERR_INTERNAL, std::string("getrandom failed: ") + std::strerror(errno));
+    }
+    got += (size_t)k;
+  }
+}
+
+// `count` <= 3 secrets in Montgomery form (a powers-of-tau contribution: tau, alpha, beta; a
+// Groth16 zkey contribution: the one factor of delta). given: count x 32 B LE, each in [1, r)
+// (NZCB_ERR_ARG "<what>: a secret is zero or not below r" otherwise). NULL: keccak256(random ||
+// entropy || k) for k < count (one byte), the digest read as a big-endian integer mod r, with 96
+// fresh bytes from the OS until none of them is zero.
+inline void make_secrets(const uint8_t* given, const uint8_t* entropy, size_t entropy_len, Fr* out, int count = 3,
+                         const char* what = "ptau") {
+  if (given) {
+    for (int k = 0; k < count; k++) {
+      Fr s;
+      std::memcpy(s.v, given + 32 * k, 32);
+      const bool ok = !s.is_zero() && !fr_noncanonical(s.v);
+      out[k] = ok ? to_mont(s) : Fr::zero();
+      wipe(&s, sizeof s);
+      if (!ok) {
+        wipe(out, (size_t)count * sizeof(Fr));
+        throw Error(NZCB_ERR_ARG, std::string(what) + ": a secret is zero or not below r");
+      }
+    }
+    return;
+  }
+  if (entropy_len && !entropy) throw Error(NZCB_ERR_ARG, "null argument");
+  std::vector<uint8_t> msg(96 + entropy_len + 1);
+  if (entropy_len) std::memcpy(msg.data() + 96, entropy, entropy_len);
+  for (bool again = true; again;) {
+    again = false;
+    os_random(msg.data(), 96);
+    for (int k = 0; k < count; k++) {
+      uint8_t dg[32];
+      msg.back() = (uint8_t)k;
+      keccak256(msg.data(), msg.size(), dg);
+      Fr s;
+      for (int i = 0; i < 8; i++)
+        s.v[i] = (uint32_t)dg[31 - 4 * i] | (uint32_t)dg[30 - 4 * i] << 8 | (uint32_t)dg[29 - 4 * i] << 16 |
+                 (uint32_t)dg[28 - 4 * i] << 24;
+      for (int i = 0; i < 6; i++) s = reduce_once(s);  // 2^256 < 6 r
+      again = again || s.is_zero();
+      out[k] = to_mont(s);
+      wipe(&s, sizeof s);
+      wipe(dg, sizeof dg);
+    }
+  }
+  wipe(msg.data(), msg.size());
 }
 
 }  // namespace nzcb

@@ -148,35 +148,7 @@ struct CallClock {
 constexpr int kDefaultBatchTop = 16;
 int g_batch_top = kDefaultBatchTop;
 
-void wipe(void* p, size_t n) {
-  volatile uint8_t* b = static_cast<volatile uint8_t*>(p);
-  for (size_t i = 0; i < n; i++) b[i] = 0;
-}
-
-struct Tally {  // defective points and the lowest one's key (key_check.h srs_bad_key)
-  uint64_t n_bad = 0, key = kNoBadKey;
-};
-
 // ---------------------------------------------------------------- backends
-// fn(i) for i < n on up to 16 threads of the host
-template <class Fn>
-void parallel_for(uint64_t n, Fn fn) {
-  const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-  const unsigned nt = (unsigned)std::min<uint64_t>(std::min(16u, hw), n / 4);
-  if (nt <= 1) {
-    for (uint64_t i = 0; i < n; i++) fn(i);
-    return;
-  }
-  std::vector<std::thread> th;
-  for (unsigned t = 0; t < nt; t++) {
-    const uint64_t lo = n * t / nt, hi = n * (t + 1) / nt;
-    th.emplace_back([lo, hi, &fn] {
-      for (uint64_t i = lo; i < hi; i++) fn(i);
-    });
-  }
-  for (auto& t : th) t.join();
-}
-
 uint32_t bitrev_host(uint32_t x, int bits) {
   uint32_t r = 0;
   for (int b = 0; b < bits; b++) r |= ((x >> b) & 1u) << (bits - 1 - b);
@@ -353,61 +325,6 @@ struct DeviceBackend {
     for (int p = first + 1; p <= top; p++) levels<F>(d_src.p, n_src, p, p, d_x.p, d_out.p, d_tw.p, d_inv_n.p, dst);
   }
 };
-
-// ---------------------------------------------------------------- secrets
-void os_random(uint8_t* b, size_t len) {
-  size_t got = 0;
-  while (got < len) {
-    const ssize_t k = getrandom(b + got, len - got, 0);
-    if (k < 0) {
-      if (errno == EINTR || errno == EAGAIN) continue;
-      throw Error(NZCB_ERR_INTERNAL, std::string("getrandom failed: ") + std::strerror(errno));
-    }
-    got += (size_t)k;
-  }
-}
-
-// tau, alpha, beta in Montgomery form. given: 3 x 32 B LE, each in [1, r) (NZCB_ERR_ARG otherwise).
-// NULL: keccak256(random || entropy || k) for k = 0, 1, 2 (one byte), the digest read as a
-// big-endian integer mod r, with 96 fresh bytes from the OS until none of the three is zero.
-void make_secrets(const uint8_t* given, const uint8_t* entropy, size_t entropy_len, Fr out[3]) {
-  if (given) {
-    for (int k = 0; k < 3; k++) {
-      Fr s;
-      std::memcpy(s.v, given + 32 * k, 32);
-      const bool ok = !s.is_zero() && !fr_noncanonical(s.v);
-      out[k] = ok ? to_mont(s) : Fr::zero();
-      wipe(&s, sizeof s);
-      if (!ok) {
-        wipe(out, 3 * sizeof(Fr));
-        throw Error(NZCB_ERR_ARG, "ptau: a secret is zero or not below r");
-      }
-    }
-    return;
-  }
-  if (entropy_len && !entropy) throw Error(NZCB_ERR_ARG, "null argument");
-  std::vector<uint8_t> msg(96 + entropy_len + 1);
-  if (entropy_len) std::memcpy(msg.data() + 96, entropy, entropy_len);
-  for (bool again = true; again;) {
-    again = false;
-    os_random(msg.data(), 96);
-    for (int k = 0; k < 3; k++) {
-      uint8_t dg[32];
-      msg.back() = (uint8_t)k;
-      keccak256(msg.data(), msg.size(), dg);
-      Fr s;
-      for (int i = 0; i < 8; i++)
-        s.v[i] = (uint32_t)dg[31 - 4 * i] | (uint32_t)dg[30 - 4 * i] << 8 | (uint32_t)dg[29 - 4 * i] << 16 |
-                 (uint32_t)dg[28 - 4 * i] << 24;
-      for (int i = 0; i < 6; i++) s = reduce_once(s);  // 2^256 < 6 r
-      again = again || s.is_zero();
-      out[k] = to_mont(s);
-      wipe(&s, sizeof s);
-      wipe(dg, sizeof dg);
-    }
-  }
-  wipe(msg.data(), msg.size());
-}
 
 // ---------------------------------------------------------------- the operations
 template <class Be, class F>

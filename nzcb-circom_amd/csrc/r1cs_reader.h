@@ -2,7 +2,8 @@
 // linear combinations of the constraint section. Two users parse through it: the PLONK
 // setup (csrc/synth.hip circuit_from_r1cs, snarkjs `plonk setup`) and the witness check
 // (csrc/r1cs_check.hip, snarkjs `wtns check`), so a file is malformed for both in the same
-// words.
+// words. The Groth16 setup (csrc/groth16.h) reads its constraints through it too. The header
+// needs no HIP runtime.
 #pragma once
 #include <cstdint>
 #include <cstdio>
@@ -10,7 +11,8 @@
 #include <utility>
 #include <vector>
 
-#include "common.h"
+#include "capi_guard.h"
+#include "field.h"
 
 namespace nzcb {
 

@@ -1002,6 +1002,107 @@ napi_value PtauOp(napi_env env, napi_callback_info info) {
   return promise;
 }
 
+// one zKey.newZKey / zKey.contribute call for a Groth16 key (nzcb_groth16_setup_file,
+// nzcb_groth16_contribute_file) on a worker thread (async work); the promise is settled on the
+// main thread. Files are mapped and written by the library.
+struct Groth16OpWork {
+  napi_deferred deferred = nullptr;
+  napi_async_work work = nullptr;
+  int kind = 0;  // 0 setup, 1 contribute
+  int device = 0;
+  std::string a, b, out_path, entropy;
+  int rc = 0;
+  nzcb_err err{};
+};
+
+void groth16_op_execute(napi_env, void* data) {
+  Groth16OpWork* w = static_cast<Groth16OpWork*>(data);
+  if (w->kind == 0)
+    w->rc = nzcb_groth16_setup_file(w->a.c_str(), w->b.c_str(), w->out_path.c_str(), w->device, &w->err);
+  else
+    w->rc = nzcb_groth16_contribute_file(w->a.c_str(), w->out_path.c_str(), nullptr,
+                                         reinterpret_cast<const uint8_t*>(w->entropy.data()), w->entropy.size(),
+                                         w->device, &w->err);
+}
+
+void groth16_op_complete(napi_env env, napi_status status, void* data) {
+  Groth16OpWork* w = static_cast<Groth16OpWork*>(data);
+  if (status != napi_ok || w->rc != 0) {
+    napi_reject_deferred(env, w->deferred,
+                         make_error(env, w->rc ? w->err.code : NZCB_ERR_INTERNAL,
+                                    w->rc ? w->err.msg : "groth16Op: the work was cancelled"));
+  } else {
+    napi_value undef;
+    napi_get_undefined(env, &undef);
+    napi_resolve_deferred(env, w->deferred, undef);
+  }
+  napi_delete_async_work(env, w->work);
+  delete w;
+}
+
+// groth16Op(kind: 0 = setup | 1 = contribute, a: string (the r1cs, or the old zkey), b: string (the
+//   ptau; ignored for contribute), out: string (the zkey written), entropy: string, device: number)
+//   -> Promise<undefined>. The secret of a contribution is drawn inside the library.
+napi_value Groth16Op(napi_env env, napi_callback_info info) {
+  size_t argc = 6;
+  napi_value argv[6];
+  CHECK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  Groth16OpWork* w = new Groth16OpWork();
+  int32_t kind = -1, device = 0;
+  bool ok = argc >= 4 && napi_get_value_int32(env, argv[0], &kind) == napi_ok && kind >= 0 && kind <= 1 &&
+            str_arg(env, argv[1], &w->a) && (kind == 1 || str_arg(env, argv[2], &w->b)) &&
+            str_arg(env, argv[3], &w->out_path);
+  if (ok && argc > 4) (void)str_arg(env, argv[4], &w->entropy);
+  if (ok && argc > 5) napi_get_value_int32(env, argv[5], &device);
+  if (!ok) {
+    delete w;
+    napi_throw_type_error(env, nullptr, "groth16Op(kind: 0 | 1, a: string, b: string, out: string, entropy?, device?)");
+    return nullptr;
+  }
+  w->kind = kind;
+  w->device = device;
+  napi_value promise, name;
+  if (napi_create_promise(env, &w->deferred, &promise) != napi_ok ||
+      napi_create_string_utf8(env, "nzcb.groth16Op", NAPI_AUTO_LENGTH, &name) != napi_ok ||
+      napi_create_async_work(env, nullptr, name, groth16_op_execute, groth16_op_complete, w, &w->work) != napi_ok ||
+      napi_queue_async_work(env, w->work) != napi_ok) {
+    delete w;
+    napi_throw_error(env, nullptr, "nzcb addon: N-API call failed");
+    return nullptr;
+  }
+  return promise;
+}
+
+// groth16Vk(zkey: string (file name, memory-mapped) | Buffer) -> string: the verification key of
+// a Groth16 zkey as JSON (nzcb_groth16_vk_to_json); throws with .code for any other file.
+napi_value Groth16Vk(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1];
+  CHECK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  std::string path;
+  const uint8_t* z = nullptr;
+  size_t zl = 0;
+  const bool from_file = argc >= 1 && str_arg(env, argv[0], &path);
+  if (!from_file && (argc < 1 || !buf_arg(env, argv[0], &z, &zl))) {
+    napi_throw_type_error(env, nullptr, "groth16Vk(zkey: string | Buffer)");
+    return nullptr;
+  }
+  auto call = [&](char* out, size_t cap) {
+    return from_file ? nzcb_groth16_vk_to_json_file(path.c_str(), out, cap) : nzcb_groth16_vk_to_json(z, zl, out, cap);
+  };
+  std::string s(256, '\0');
+  int rc = call(&s[0], s.size());
+  if (rc < 0) {
+    s.assign((size_t)-rc, '\0');
+    rc = call(&s[0], s.size());
+  }
+  if (rc != 0) {
+    napi_throw(env, make_error(env, rc, s.c_str()));
+    return nullptr;
+  }
+  return json_string(env, std::string(s.c_str()));
+}
+
 // one p256Verify call: the key's tables built (nzcb_p256_key_create), the batch verified
 // (nzcb_p256_verify) and the key released, on a worker thread (async work); the promise is
 // settled on the main thread. The inputs are copied.
@@ -1387,6 +1488,8 @@ napi_value Init(napi_env env, napi_value exports) {
       {"wtnsCheck", nullptr, WtnsCheck, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"keyCheck", nullptr, KeyCheck, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"ptauOp", nullptr, PtauOp, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"groth16Op", nullptr, Groth16Op, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"groth16Vk", nullptr, Groth16Vk, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"r1csInfo", nullptr, R1csInfo, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"p256Verify", nullptr, P256Verify, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"nzcpDecode", nullptr, NzcpDecode, nullptr, nullptr, nullptr, napi_default, nullptr},

@@ -32,6 +32,15 @@
 //   node cli.js powersoftau prepare phase2 <pot_0001.ptau> <pot_final.ptau> -v
 //     (contribute draws its secrets from the OS, mixed with -e=<entropy>; it writes NO contribution
 //     record, so `snarkjs powersoftau verify` does not accept the file; NZCB_DEVICE=-1 runs on the host)
+// and the first three lines of the `phase2` recipe for Groth16, with only the program name changed:
+//   node cli.js groth16 setup <circuit.r1cs> <pot_final.ptau> <circuit_0000.zkey> -v
+//   node cli.js zkey contribute <circuit_0000.zkey> <circuit_0001.zkey> --name="1st Contributor Name" -v
+//   node cli.js zkey export verificationkey <circuit_0001.zkey> <verification_key.json>
+//     (a fresh key has delta = 1: anyone can forge proofs under it until it has been contributed
+//     to. Setup writes NO circuit hash and contribute NO contribution record, so `snarkjs zkey
+//     verify` does not accept the files, and their parity with snarkjs's bytes is unpinned. There is
+//     no Groth16 prover, verifier or Solidity verifier here: `zkey export solidityverifier` on a
+//     Groth16 key exits non-zero. NZCB_DEVICE=-1 runs on the host)
 // Output JSON is written like snarkjs's CLI (stringifyBigInts, 1-space indent).
 const fs = require('fs');
 const nz = require('./index.js');
@@ -51,7 +60,12 @@ function usage() {
                 '       cli.js nzcp verify <file with one pass URI per line> [example | <x> <y>]\n' +
                 '       cli.js powersoftau new bn128 <power> <new.ptau> [-v]\n' +
                 '       cli.js powersoftau contribute <old.ptau> <new.ptau> [--name=<text>] [-e=<entropy>] [-v]\n' +
-                '       cli.js powersoftau prepare phase2 <old.ptau> <new.ptau> [-v]');
+                '       cli.js powersoftau prepare phase2 <old.ptau> <new.ptau> [-v]\n' +
+                '       cli.js groth16 setup <r1cs> <ptau> <zkey> [-v]\n' +
+                '       cli.js zkey contribute <old.zkey> <new.zkey> [--name=<text>] [-e=<entropy>] [-v]\n' +
+                '         (groth16 setup writes a key with delta = 1: contribute before use. NO circuit hash and NO\n' +
+                '         contribution record are written: snarkjs zkey verify does not accept these files. There is\n' +
+                '         no Groth16 prover, verifier or Solidity verifier here.)');
   process.exit(1);
 }
 
@@ -115,8 +129,31 @@ async function phase1(argv) {
   usage();
 }
 
+// groth16 setup | zkey contribute with the same options
+async function phase2(argv) {
+  const opts = { name: '', entropy: '' };
+  const args = [];
+  for (const a of argv.slice(1)) {
+    const m = /^(--name|-n|--entropy|-e)=(.*)$/s.exec(a);
+    if (m) opts[m[1] === '--name' || m[1] === '-n' ? 'name' : 'entropy'] = m[2];
+    else if (a === '-v' || a === '--verbose') continue;
+    else if (a.startsWith('-')) usage();
+    else args.push(a);
+  }
+  // the CLI always says what the file is not, -v or not
+  const say = { info: (m) => console.log(m) };
+  if (argv[0] === 'groth16' && args[0] === 'setup' && args.length === 4) {
+    return nz.zKey.newZKey(args[1], args[2], args[3], say);
+  }
+  if (argv[0] === 'zkey' && args[0] === 'contribute' && args.length === 3) {
+    return nz.zKey.contribute(args[1], args[2], opts.name, opts.entropy, say);
+  }
+  usage();
+}
+
 async function main(argv) {
   if (argv[0] === 'powersoftau' && (argv[1] === 'new' || argv[1] === 'contribute' || argv[1] === 'prepare')) return phase1(argv);
+  if (argv[0] === 'groth16' || (argv[0] === 'zkey' && argv[1] === 'contribute')) return phase2(argv);
   if (argv[0] === 'zkey' && argv[1] === 'check' && argv.length === 3) return keyCheck(argv);
   if (argv[0] === 'powersoftau' && argv[1] === 'check' && (argv.length === 3 || argv.length === 4)) return keyCheck(argv);
   if (argv[0] === 'zkey') return zkeyExport(argv);

@@ -421,8 +421,78 @@ function vkOf(zkey) {
   return typeof zkey === 'string' ? addon.vkFromZkeyFile(zkey) : addon.vkFromZkey(readBin(zkey));
 }
 
+// the protocol id of a zkey (section 1: 1 = groth16, 2 = plonk), read through its section table;
+// 0 for anything that is no zkey
+function zkeyProtocol(zkey) {
+  const fd = typeof zkey === 'string' ? fs.openSync(zkey, 'r') : null;
+  const bytes = fd === null ? readBin(zkey) : null;
+  const read = (pos, len) => {
+    const b = Buffer.alloc(len);
+    if (fd === null) return bytes.copy(b, 0, pos, pos + len) === len ? b : null;
+    return fs.readSync(fd, b, 0, len, pos) === len ? b : null;
+  };
+  try {
+    const head = read(0, 12);
+    if (!head || head.toString('latin1', 0, 4) !== 'zkey') return 0;
+    let pos = 12;
+    for (let i = head.readUInt32LE(8); i > 0; i--) {
+      const entry = read(pos, 12);
+      if (!entry) return 0;
+      if (entry.readUInt32LE(0) === 1) {
+        const id = read(pos + 12, 4);
+        return id ? id.readUInt32LE(0) : 0;
+      }
+      pos += 12 + Number(entry.readBigUInt64LE(4));
+    }
+    return 0;
+  } finally {
+    if (fd !== null) fs.closeSync(fd);
+  }
+}
+
+// snarkjs zKey.exportVerificationKey: by the key's protocol id, the PLONK object or, for a Groth16
+// key (id 1), {protocol: "groth16", curve, nPublic, vk_alpha_1, vk_beta_2, vk_gamma_2, vk_delta_2,
+// IC}. snarkjs's vk_alphabeta_12 is left out: its Fq12 layout cannot be pinned here, and neither
+// snarkjs's verifier nor its Solidity template reads it.
 async function exportVerificationKey(zkeyFileName) {
+  if (zkeyProtocol(zkeyFileName) === 1) {
+    return JSON.parse(addon.groth16Vk(typeof zkeyFileName === 'string' ? zkeyFileName : readBin(zkeyFileName)));
+  }
   return JSON.parse(addon.vkToJson(vkOf(zkeyFileName)));
+}
+
+// snarkjs's `phase2` recipe for Groth16 (include/nzcb.h nzcb_groth16_setup,
+// nzcb_groth16_contribute), with snarkjs's names and argument order, file names only; each runs on
+// a worker thread. NZCB_DEVICE selects the GPU (-1 = on the host) when options.device is not given.
+// zKey.newZKey(r1csName, ptauName, zkeyName, logger): the Groth16 proving key of the circuit from
+//   a powers-of-tau file prepared for phase 2. A FRESH KEY HAS delta = 1: anyone can forge proofs
+//   under it until zKey.contribute has run. No circuit hash is written and the bytes' parity with
+//   snarkjs is unpinned.
+// zKey.contribute(oldZkeyName, newZkeyName, name, entropy, logger): multiplies a fresh secret from
+//   the OS CSPRNG, mixed with `entropy`, into delta. NO contribution record is written (`name` is
+//   only logged), so `snarkjs zkey verify` does not accept the result.
+async function newZKey(r1csName, ptauName, zkeyName, logger, options) {
+  if (typeof r1csName !== 'string' || typeof ptauName !== 'string' || typeof zkeyName !== 'string') {
+    throw new TypeError('newZKey: file names must be strings');
+  }
+  await addon.groth16Op(0, r1csName, ptauName, zkeyName, '', ptauDevice(options));
+  const log = ptauLog(logger);
+  if (log) {
+    log('groth16 setup: key written with delta = 1 (contribute before use); NO circuit hash written ' +
+        '(snarkjs zkey verify will not accept this file)');
+  }
+}
+async function zkeyContribute(oldZkeyName, newZkeyName, name, entropy, logger, options) {
+  if (typeof oldZkeyName !== 'string' || typeof newZkeyName !== 'string') {
+    throw new TypeError('contribute: file names must be strings');
+  }
+  await addon.groth16Op(1, oldZkeyName, '', newZkeyName, entropy === undefined || entropy === null ? '' : String(entropy),
+                        ptauDevice(options));
+  const log = ptauLog(logger);
+  if (log) {
+    log(`zkey contribute: "${name || ''}" applied (the name is not recorded); NO contribution record written ` +
+        '(snarkjs zkey verify will not accept this file)');
+  }
 }
 
 // snarkjs zKey.exportSolidityVerifier(zkeyName, templates, logger) (`zkey export
@@ -431,6 +501,7 @@ async function exportVerificationKey(zkeyFileName) {
 // options.name sets the contract name (the reference's deploy-script.js asks for "Verifier").
 async function exportSolidityVerifier(zkeyFileName, templates, logger, options) {
   options = options || {};
+  if (zkeyProtocol(zkeyFileName) === 1) throw new Error('groth16: the Solidity verifier is not implemented');
   const tp = options.transcriptPublic === undefined ? true : !!options.transcriptPublic;
   const src = addon.vkToSolidity(vkOf(zkeyFileName), options.name || 'PlonkVerifier', tp);
   const log = loggerFn(logger);
@@ -866,7 +937,7 @@ async function verifyPass(uri, options) {
 
 module.exports = {
   plonk: { setup, prove, fullProve, verify, verifyBatch, exportSolidityCallData },
-  zKey: { exportVerificationKey, exportSolidityVerifier, check: zKeyCheck },
+  zKey: { exportVerificationKey, exportSolidityVerifier, check: zKeyCheck, newZKey, contribute: zkeyContribute },
   powersOfTau: { check: powersOfTauCheck, newAccumulator, contribute, preparePhase2 },
   nzcp: Object.assign({}, nzcpHost, { witness: nzcpWitness, verifyPass, verifyPasses, p256Verify, decodePasses }),
   wtns: { calculate: wtnsCalculate, remapProgram, check: wtnsCheck },

@@ -58,6 +58,9 @@ EXPORTED_SYMBOLS = [
     "nzcb_ptau_new", "nzcb_ptau_new_file", "nzcb_ptau_contribute", "nzcb_ptau_contribute_file",
     "nzcb_ptau_prepare_phase2", "nzcb_ptau_prepare_phase2_file", "nzcb_debug_ptau_timings",
     "nzcb_debug_ptau_batch_top",
+    "nzcb_groth16_setup", "nzcb_groth16_setup_file", "nzcb_groth16_contribute", "nzcb_groth16_contribute_file",
+    "nzcb_groth16_vk_to_json", "nzcb_groth16_vk_to_json_file", "nzcb_engine_groth16_rows",
+    "nzcb_debug_groth16_schedule", "nzcb_debug_groth16_timings",
 ]
 
 NZCB_FAULT_QUOTIENT = 1  # include/nzcb_internal.h
@@ -76,6 +79,7 @@ PASS_HAS_ALG, PASS_HAS_KID, PASS_HAS_ISS, PASS_HAS_NBF, PASS_HAS_EXP, PASS_HAS_C
     1, 2, 4, 8, 16, 32, 64)  # include/nzcb.h NZCB_PASS_HAS_*
 KEY_HOST = -1  # include/nzcb.h NZCB_KEY_HOST: the key material check on the host
 PTAU_HOST = -1  # include/nzcb.h NZCB_PTAU_HOST: the powers-of-tau operations on the host
+GROTH16_HOST = -1  # include/nzcb.h NZCB_GROTH16_HOST: Groth16 setup and zkey contribute on the host
 KEY_STATUS_NAMES = ("OK", "G2", "RANGE", "CURVE", "GENERATOR", "SEQUENCE", "COSETS", "NONCANONICAL", "LAGRANGE",
                     "EVALS", "COMMIT")  # include/nzcb.h NZCB_KEY_*
 KEY_PARTS = ("Qm", "Ql", "Qr", "Qo", "Qc", "S1", "S2", "S3")  # nzcb_zkey_check's parts 0..7, then L0, L1, ...
@@ -340,6 +344,19 @@ def load(path: str | None = None):
         "nzcb_ptau_prepare_phase2_file": (c_int, [ctypes.c_char_p, ctypes.c_char_p, c_int, POINTER(_Err)]),
         "nzcb_debug_ptau_timings": (c_int, [POINTER(c_double), c_int]),
         "nzcb_debug_ptau_batch_top": (c_int, [c_int]),
+        "nzcb_groth16_setup": (c_int, [c_void_p, c_size_t, c_void_p, c_size_t, c_int, POINTER(POINTER(c_uint8)),
+                                       POINTER(c_size_t), POINTER(_Err)]),
+        "nzcb_groth16_setup_file": (c_int, [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, c_int, POINTER(_Err)]),
+        "nzcb_groth16_contribute": (c_int, [c_void_p, c_size_t, u8p, ctypes.c_char_p, c_size_t, c_int,
+                                            POINTER(POINTER(c_uint8)), POINTER(c_size_t), POINTER(_Err)]),
+        "nzcb_groth16_contribute_file": (c_int, [ctypes.c_char_p, ctypes.c_char_p, u8p, ctypes.c_char_p, c_size_t,
+                                                 c_int, POINTER(_Err)]),
+        "nzcb_groth16_vk_to_json": (c_int, [c_void_p, c_size_t, ctypes.c_char_p, c_size_t]),
+        "nzcb_groth16_vk_to_json_file": (c_int, [ctypes.c_char_p, ctypes.c_char_p, c_size_t]),
+        "nzcb_engine_groth16_rows": (c_int, [c_int, c_int, c_void_p, ctypes.c_uint64, POINTER(ctypes.c_uint64),
+                                             ctypes.c_uint64, POINTER(c_uint32), u8p, u8p, POINTER(_Err)]),
+        "nzcb_debug_groth16_schedule": (c_int, [c_int, c_int, POINTER(c_int), POINTER(c_int)]),
+        "nzcb_debug_groth16_timings": (c_int, [POINTER(c_double), c_int]),
     }
     lib.missing_symbols = []
     for name, (res, args) in sigs.items():
@@ -1953,6 +1970,158 @@ def ptau_timings() -> list:
     ms = (c_double * 2)()
     k = load().nzcb_debug_ptau_timings(ms, 2)
     return list(ms[:k])
+
+
+def _read_if_path(x):
+    if _is_path(x):
+        with open(x, "rb") as f:
+            return f.read()
+    return x
+
+
+def groth16_setup(r1cs_or_path, ptau_or_path, out_path=None, device: int = 0):
+    """snarkjs ``groth16 setup <r1cs> <ptau> <zkey>``: the Groth16 proving key of a circuit from a
+    powers-of-tau file that ptau_prepare_phase2 prepared, every key point a sparse sum of
+    coefficients times Lagrange points computed on GPU `device` (GROTH16_HOST: on the host;
+    include/nzcb.h nzcb_groth16_setup, where the file layout is specified). A FRESH KEY HAS
+    delta = gamma = 1: anyone can forge proofs under it until groth16_contribute has run. NO
+    circuit hash and NO contribution records are written, so ``snarkjs zkey verify`` does not
+    accept the key, and parity with snarkjs's bytes is unpinned. The inputs are bytes or paths
+    (memory-mapped when both are paths and `out_path` is given). Returns the bytes, or writes
+    `out_path` and returns it."""
+    lib = load()
+    err = _Err()
+    if _is_path(r1cs_or_path) and _is_path(ptau_or_path) and out_path is not None:
+        _check(lib.nzcb_groth16_setup_file(os.fsencode(r1cs_or_path), os.fsencode(ptau_or_path),
+                                           os.fsencode(out_path), device, ctypes.byref(err)), err)
+        return out_path
+    rp, rn, keep_r = _host_view(_read_if_path(r1cs_or_path))
+    pp_, pn, keep_p = _host_view(_read_if_path(ptau_or_path))
+    zp, zl = POINTER(c_uint8)(), c_size_t()
+    rc = lib.nzcb_groth16_setup(rp, rn, pp_, pn, device, ctypes.byref(zp), ctypes.byref(zl), ctypes.byref(err))
+    del keep_r, keep_p
+    _check(rc, err)
+    out = _take_ptau(lib, zp, zl)
+    if out_path is None:
+        return out
+    with open(out_path, "wb") as f:
+        f.write(out)
+    return out_path
+
+
+def groth16_contribute(zkey_or_path, out_path=None, secret=None, entropy=None, device: int = 0):
+    """snarkjs ``zkey contribute``: multiply your own secret d into a Groth16 key on GPU `device`
+    (GROTH16_HOST: on the host): delta1 and delta2 by d, C and H by 1/d; everything else is copied
+    (include/nzcb.h nzcb_groth16_contribute). secret = None draws d from the OS CSPRNG, mixed with
+    the optional `entropy` (str or bytes); an integer in [1, r) is FOR REPRODUCIBLE TESTS ONLY.
+    The points of C and H and the two deltas are tested first; a bad one raises NzcbError FORMAT
+    naming its section and index. NO contribution record is written: ``snarkjs zkey verify`` does
+    not accept the output. The input is bytes, or a path (memory-mapped when `out_path` is given).
+    Returns the bytes, or writes `out_path` and returns it."""
+    lib = load()
+    err = _Err()
+    sec = None
+    if secret is not None:
+        if not 0 <= int(secret) < 1 << 256:
+            raise NzcbError(1, "zkey: a secret is zero or not below r")
+        sec = _buf(int(secret).to_bytes(32, "little"))
+    ent = entropy.encode() if isinstance(entropy, str) else bytes(entropy or b"")
+    if _is_path(zkey_or_path) and out_path is not None:
+        _check(lib.nzcb_groth16_contribute_file(os.fsencode(zkey_or_path), os.fsencode(out_path), sec, ent, len(ent),
+                                                device, ctypes.byref(err)), err)
+        return out_path
+    ptr, n, keep = _host_view(_read_if_path(zkey_or_path))
+    zp, zl = POINTER(c_uint8)(), c_size_t()
+    rc = lib.nzcb_groth16_contribute(ptr, n, sec, ent, len(ent), device, ctypes.byref(zp), ctypes.byref(zl),
+                                     ctypes.byref(err))
+    del keep
+    _check(rc, err)
+    out = _take_ptau(lib, zp, zl)
+    if out_path is None:
+        return out
+    with open(out_path, "wb") as f:
+        f.write(out)
+    return out_path
+
+
+def groth16_vk(zkey_or_path) -> dict:
+    """snarkjs ``zkey export verificationkey`` for a Groth16 key (bytes, or a path, which is
+    memory-mapped): protocol, curve, nPublic, vk_alpha_1, vk_beta_2, vk_gamma_2, vk_delta_2, IC
+    (include/nzcb.h nzcb_groth16_vk_to_json). snarkjs's vk_alphabeta_12 is left out."""
+    lib = load()
+    if _is_path(zkey_or_path):
+        def call(out, cap):
+            return lib.nzcb_groth16_vk_to_json_file(os.fsencode(zkey_or_path), out, cap)
+    else:
+        ptr, n, keep = _host_view(zkey_or_path)
+
+        def call(out, cap):
+            return lib.nzcb_groth16_vk_to_json(ptr, n, out, cap)
+    out = ctypes.create_string_buffer(256)
+    rc = call(out, 256)
+    if rc < 0:
+        out = ctypes.create_string_buffer(-rc)
+        rc = call(out, -rc)
+    if rc != 0:
+        raise NzcbError(rc, out.value.decode(errors="replace"))
+    return json.loads(out.value.decode())
+
+
+def groth16_rows(points: bytes, row_off, idx, coefs, g2: bool = False, device: int = 0) -> list:
+    """Tests: the kernel family of groth16_setup on bare arrays (nzcb_engine_groth16_rows). points:
+    LEM affine points back to back (64 B each, 128 B with g2); row r is the sum over t in
+    [row_off[r], row_off[r + 1]) of coefs[t] * points[idx[t]], coefs integers in [0, r). Returns
+    one LEM affine point per row (zero bytes: the point at infinity). On a GPU the points are
+    uploaded first, as the entry point reads them from device memory."""
+    lib = load()
+    w = 128 if g2 else 64
+    n_points, n_rows, n_terms = len(points) // w, len(row_off) - 1, len(idx)
+    ro = (ctypes.c_uint64 * (n_rows + 1))(*row_off)
+    ix = (c_uint32 * max(n_terms, 1))(*idx)
+    cf = _buf(b"".join(int(c).to_bytes(32, "little") for c in coefs))
+    out = _out(w * n_rows)
+    err = _Err()
+    if device == GROTH16_HOST:
+        src = _buf(points)
+        rc = lib.nzcb_engine_groth16_rows(device, int(g2), ctypes.cast(src, c_void_p), n_points, ro, n_rows, ix, cf,
+                                          out, ctypes.byref(err))
+    else:
+        d_pts = lib.nzcb_dev_alloc_on(device, max(len(points), 4))
+        if not d_pts:
+            raise NzcbError(10, "hipMalloc failed")
+        try:
+            if points:
+                h2d(d_pts, points)
+            rc = lib.nzcb_engine_groth16_rows(device, int(g2), d_pts, n_points, ro, n_rows, ix, cf, out,
+                                              ctypes.byref(err))
+        finally:
+            lib.nzcb_dev_free(d_pts)
+    _check(rc, err)
+    return [bytes(out[w * i:w * i + w]) for i in range(n_rows)]
+
+
+def groth16_schedule(chunk: int, fan_in: int) -> tuple:
+    """Tests: the longest chunk of a row one lane sums and the fan-in of the folds that follow, for
+    the calls after this one (nzcb_debug_groth16_schedule; <= 0 restores the library's constant).
+    Returns the previous (chunk, fan_in). The bytes of a key do not depend on them."""
+    pc, pf = c_int(), c_int()
+    rc = load().nzcb_debug_groth16_schedule(chunk, fan_in, ctypes.byref(pc), ctypes.byref(pf))
+    if rc != 0:
+        raise NzcbError(rc, "groth16: chunk length in 1..1024 and fan-in in 2..1024")
+    return pc.value, pf.value
+
+
+GROTH16_TIMING_NAMES = ("kernels_ms", "call_ms", "rows_g1_ms", "rows_g2_ms", "tests_ms", "scale_ms", "plan_ms",
+                        "terms_A", "terms_B1", "terms_B2", "terms_K", "chunks_g1", "chunks_g2")
+
+
+def groth16_timings() -> dict:
+    """This thread's last groth16_setup, groth16_contribute or groth16_rows: kernel milliseconds
+    (HIP events) by step, the call's wall time, and the term and chunk counts
+    (nzcb_debug_groth16_timings)."""
+    v = (c_double * len(GROTH16_TIMING_NAMES))()
+    k = load().nzcb_debug_groth16_timings(v, len(GROTH16_TIMING_NAMES))
+    return dict(zip(GROTH16_TIMING_NAMES[:k], v[:k]))
 
 
 def synth_setup_raw(power: int, n_public: int = 3, n_inputs: int = 8, seed: int = 0x6E7A6362,
