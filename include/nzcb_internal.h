@@ -47,6 +47,28 @@ int nzcb_debug_guard_selftest(int device, nzcb_err* err);
 #define NZCB_FAULT_LANE_ALLOC 3
 int nzcb_debug_inject_fault(nzcb_ctx* ctx, int kind);
 
+/* ---- The signal basis (csrc/sigbasis.h): A, B, C committed over the witness signals ---------- */
+/* The expansion of a key's additions gives up, and the context commits from the Lagrange basis,
+ * past per_constraint * 3 * nConstraints terms (the library's constant is 64; < 0 restores it).
+ * Sets it for the contexts created after the call and returns the previous value. For tests. */
+int nzcb_debug_signal_basis_cap(int per_constraint);
+/* out[0] = 1 if the context commits A, B, C over the signal basis, [1..3] the rows (signals
+ * present) of A, B, C, [4] the points per set in the table (the most rows + 2), [5] the (set,
+ * signal, gate) terms of the expansion, [6] the bytes of the signal table. */
+int nzcb_debug_signal_basis_info(const nzcb_ctx* ctx, uint64_t out[7]);
+/* A, B and C's commitments of a witness (n_witness x 32 B LE normal form, which need not satisfy
+ * the circuit) under `blinding` (11 x 32 B, as nzcb_prove_witness) without a proof: out = 3 x 64 B
+ * affine LEM. signal_basis = 1: over the signal basis; 0: over the Lagrange basis, the three in one
+ * schedule. NZCB_ERR_ARG when the context does not have that path. Runs on lane 0 with no proof
+ * in flight. */
+int nzcb_debug_commit_abc(nzcb_ctx* ctx, const uint8_t* witness, size_t n_witness, const uint8_t* blinding,
+                          int signal_basis, uint8_t* out, nzcb_err* err);
+/* The signal basis's rows of set 0, 1, 2 (A, B, C), compacted to the signals that have one:
+ * rows_out = info[1 + set] x 64 B affine LEM, signals_out = their signal indices, ascending (cap:
+ * the rows both arrays hold). A signal not listed has no row in the set. */
+int nzcb_debug_signal_rows(nzcb_ctx* ctx, int set, uint8_t* rows_out, uint32_t* signals_out, size_t cap,
+                           nzcb_err* err);
+
 /* The 9x29-bit products of csrc/f29.h as compiled for the device (the generated column asm),
  * over `count` host items of 32-bit limb words (9 per value), for tests against exact
  * integers. op 1: mul_shoup(x, w, ws) (27 words in, 9 out); 2: mul_shoup_x2 (54 / 18);

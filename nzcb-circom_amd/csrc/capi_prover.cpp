@@ -11,6 +11,7 @@
 
 #include "../../include/nzcb_internal.h"
 #include "prover.h"
+#include "sigbasis.h"
 
 namespace nzcb {
 
@@ -472,6 +473,38 @@ int nzcb_debug_inject_fault(nzcb_ctx* ctx, int kind) {
   ctx->pending_fault = kind;
   if (kind == 0) ctx->lane_alloc_fault = 0;
   return 0;
+}
+
+int nzcb_debug_signal_basis_cap(int per_constraint) { return (int)sig_basis_cap(per_constraint < 0 ? -1 : per_constraint); }
+
+int nzcb_debug_signal_basis_info(const nzcb_ctx* ctx, uint64_t out[7]) {
+  if (!ctx || !out) return NZCB_ERR_ARG;
+  const Prover& p = *ctx->p;
+  out[0] = p.sigcommit ? 1 : 0;
+  for (int k = 0; k < 3; k++) out[1 + k] = p.sig_cnt[k];
+  out[4] = p.sig_stride;
+  out[5] = p.sig_terms;
+  out[6] = p.stab.q.n * sizeof(G1Affine);
+  return 0;
+}
+
+int nzcb_debug_commit_abc(nzcb_ctx* ctx, const uint8_t* witness, size_t n_witness, const uint8_t* blinding,
+                          int signal_basis, uint8_t* out, nzcb_err* err) {
+  if (!ctx) return fail(err, NZCB_ERR_ARG, "null argument");
+  return guarded(err, [&] {
+    std::unique_lock<std::shared_mutex> lk(ctx->cfg);  // lane 0, with no proof in flight
+    ctx->p->debug_commit_abc(witness, n_witness, blinding, signal_basis != 0, out);
+  });
+}
+
+int nzcb_debug_signal_rows(nzcb_ctx* ctx, int set, uint8_t* rows_out, uint32_t* signals_out, size_t cap,
+                           nzcb_err* err) {
+  if (!ctx) return fail(err, NZCB_ERR_ARG, "null argument");
+  return guarded(err, [&] {
+    std::unique_lock<std::shared_mutex> lk(ctx->cfg);
+    if (set < 0 || set > 2 || cap < ctx->p->sig_cnt[set]) throw Error(NZCB_ERR_ARG, "signal rows: set 0..2, cap >= its rows");
+    ctx->p->debug_signal_rows(set, rows_out, signals_out);
+  });
 }
 
 int nzcb_proof_to_json(const uint8_t* proof, char* out, size_t cap) {

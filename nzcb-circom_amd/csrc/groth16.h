@@ -237,6 +237,11 @@ inline G16Plan g16_plan(G16Rows& r, uint32_t chunk, uint32_t fan_in) {
   return p;
 }
 
+// The G1 rows of r over points already on `device` (groth16.hip k_g16_chunks, k_g16_fold,
+// k_g16_store on a stream of the call's own), affine LEM into host memory at `out`; zero bytes for
+// an empty row. The prover's signal basis is built with it (sigbasis.hip).
+void g16_rows_g1_device(int device, const G1Pt* d_pts, const G16Rows& r, const G16Plan& plan, uint8_t* out);
+
 // ---------------------------------------------------------------- schedule knob and timings
 struct G16Schedule {
   uint32_t chunk = kG16DefaultChunk, fan_in = kG16DefaultFanIn;

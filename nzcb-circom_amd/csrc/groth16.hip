@@ -238,6 +238,11 @@ void give(PtauOut& o, uint8_t** out, size_t* out_len) {
 
 }  // namespace
 
+void g16_rows_g1_device(int device, const G1Pt* d_pts, const G16Rows& r, const G16Plan& plan, uint8_t* out) {
+  G16DeviceBackend be(device);
+  be.rows_on<Fq>(d_pts, r, plan, out);
+}
+
 }  // namespace nzcb
 
 using namespace nzcb;

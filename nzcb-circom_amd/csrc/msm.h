@@ -113,9 +113,11 @@ void msm_enqueue(MsmScratch& sc, const G1Affine* bases, const Fr* scalars, size_
 G1xyzz msm_finish(MsmScratch& sc, hipStream_t st);
 // Several fixed-base MSMs over ONE table in one schedule (MsmScratch sized with lagrange_sets >=
 // sets): one bucketing, accumulation and carry reduction over sets x 2^(c-1) buckets, window sums
-// per set (round 6: A, B, C over the Lagrange basis). scalars[s]: n values each.
+// per set (round 6: A, B, C over the Lagrange basis). scalars[s]: n values each. set_base (or
+// null: all zero): set s's scalar i multiplies the table's point set_base[s] + i, so the sets may
+// index their own segments of one table (set_base[s] + n <= table->n; the prover's signal basis).
 void msm_enqueue_sets(MsmScratch& sc, const Fr* const* scalars, int sets, size_t n, bool scalars_mont,
-                      hipStream_t st, const MsmBaseTable* table);
+                      hipStream_t st, const MsmBaseTable* table, const uint32_t* set_base = nullptr);
 void msm_finish_sets(MsmScratch& sc, hipStream_t st, G1xyzz* out);
 
 inline G1xyzz msm(MsmScratch& sc, const G1Affine* bases, const Fr* scalars, size_t n, bool mont, hipStream_t st,

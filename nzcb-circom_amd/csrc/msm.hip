@@ -311,7 +311,7 @@ __device__ __forceinline__ uint32_t scalar_min_form(Fr& s) {
 
 template <int C, int NW>
 __device__ __forceinline__ uint32_t bin_entries(const Fr* __restrict__ scalars, size_t i, int mont, size_t stride,
-                                                uint32_t (&kk)[NW], uint32_t (&vv)[NW]) {
+                                                uint32_t base, uint32_t (&kk)[NW], uint32_t (&vv)[NW]) {
   Fr s = scalars[i];
   if (mont & kDigMont) s = from_mont_fr29(s);
   const uint32_t flip = (mont & kDigMinForm) ? scalar_min_form(s) : 0u;
@@ -323,7 +323,7 @@ __device__ __forceinline__ uint32_t bin_entries(const Fr* __restrict__ scalars, 
   }
   for_each_digit<C>(s, [&](int w, uint32_t b, uint32_t sign) {
     kk[w] = b;
-    vv[w] = (uint32_t)((size_t)w * stride + i) | ((sign ^ flip) << 31);
+    vv[w] = (uint32_t)((size_t)w * stride + base + i) | ((sign ^ flip) << 31);
     live |= 1u << w;
   });
   return live;
@@ -341,10 +341,13 @@ template <int KB> struct BinKeys {
 // Several MSMs over one table in one schedule (round 6: A, B and C over the Lagrange basis):
 // set s's scalars are tiles [s tps, (s + 1) tps) of the bucketing grid and its buckets keys
 // [s nb, (s + 1) nb), so one sort, one accumulation and one carry reduction serve all of them,
-// and the window sums run per set. One set: tps = all tiles.
+// and the window sums run per set. One set: tps = all tiles. base[s]: where set s's points begin
+// in the table's rows (0: the sets share one range of points; the prover's signal basis keeps a
+// segment per set).
 static constexpr int kMaxSets = 3;
 struct BinSets {
   const Fr* p[kMaxSets];
+  uint32_t base[kMaxSets];
   uint32_t tps;  // bucketing tiles per set
   uint32_t nb;   // buckets per set
 };
@@ -365,7 +368,7 @@ msm_bin_hist_kernel(BinSets sets, size_t n, int mont, uint32_t* __restrict__ cou
     const size_t i = (size_t)lt * kTileScalars + (size_t)j * kBinThreads + threadIdx.x;
     if (i < n) {
       uint32_t kk[NW], vv[NW];
-      const uint32_t live = bin_entries<C, NW>(scalars, i, mont, 0, kk, vv);
+      const uint32_t live = bin_entries<C, NW>(scalars, i, mont, 0, 0u, kk, vv);
 #pragma unroll
       for (int w = 0; w < NW; w++)
         if ((live >> w) & 1u) atomicAdd(&h[(kk[w] + kbase) >> LO], 1u);
@@ -446,7 +449,7 @@ msm_bin_scatter_kernel(BinSets sets, size_t n, int mont, size_t stride, const ui
     const size_t i = (size_t)lt * kTileScalars + (size_t)j * kBinThreads + threadIdx.x;
     live[j] = 0;
     if (i < n) {
-      live[j] = bin_entries<C, NW>(scalars, i, mont, stride, kk[j], vv[j]);
+      live[j] = bin_entries<C, NW>(scalars, i, mont, stride, sets.base[set], kk[j], vv[j]);
 #pragma unroll
       for (int w = 0; w < NW; w++) {
         kk[j][w] += kbase;
@@ -872,9 +875,17 @@ msm_accumulate29_kernel(uint32_t chunk, const G1Affine* __restrict__ bases, cons
       else if (!starts) carry_cont[t] = out;
       else carry_own[t] = out;
       inf = true;
-      // next non-empty bucket: a linear walk (one load per bucket; a chunk crosses at
-      // most a few boundaries)
-      while (pos < e && kend <= pos) {
+      // next non-empty bucket: a short linear walk (one load per bucket; a chunk of spread
+      // digits crosses a few boundaries), then the search: sets of small values (the signal
+      // basis's A and C) leave runs of tens of thousands of empty buckets, one dependent load
+      // each (5.3 ms for their accumulation on one lane before this, 0.8 ms for the gate values')
+      for (int step = 0; pos < e && kend <= pos; step++) {
+        if (step == 4) {
+          k = find_key(offsets, nkeys, pos);
+          kstart = offsets[k];
+          kend = offsets[k + 1];
+          break;
+        }
         k++;
         kstart = kend;
         kend = offsets[k + 1];
@@ -1927,7 +1938,7 @@ static void fixed_bucketing(MsmScratch& sc, const MsmPlan& p, const BinSets& set
 }
 
 static void msm_enqueue_impl(MsmScratch& sc, const G1Affine* bases, const Fr* const* scalars, int msets, size_t n,
-                             bool mont, hipStream_t st, const MsmBaseTable* table) {
+                             bool mont, hipStream_t st, const MsmBaseTable* table, const uint32_t* set_base = nullptr) {
   const auto t_enq = std::chrono::steady_clock::now();
   struct EnqueueClock {  // host time of the enqueue, for the phase timing (nzcb_engine_time_msm2)
     MsmScratch& sc;
@@ -1945,6 +1956,8 @@ static void msm_enqueue_impl(MsmScratch& sc, const G1Affine* bases, const Fr* co
   if (!sc.done) NZ_HIP(hipEventCreateWithFlags(&sc.done, hipEventDisableTiming));
   if (n > sc.max_points) throw Error(NZCB_ERR_ARG, "msm larger than scratch");
   if (table && n > table->n) throw Error(NZCB_ERR_ARG, "msm larger than its base table");
+  for (int k = 0; table && set_base && k < msets; k++)
+    if ((size_t)set_base[k] + n > table->n) throw Error(NZCB_ERR_ARG, "msm sets: a set's points lie past the base table");
   if (table && table->mont_folded && !mont) throw Error(NZCB_ERR_ARG, "2^-256-folded table needs Montgomery scalars");
   if (table && (!sc.buckets29.p || !sc.bin_counts.p))
     throw Error(NZCB_ERR_ARG, "msm scratch was not sized for the fixed-base schedule");
@@ -2014,7 +2027,10 @@ static void msm_enqueue_impl(MsmScratch& sc, const G1Affine* bases, const Fr* co
   mark(0);
   if (table) {
     BinSets bs{};
-    for (int k = 0; k < msets; k++) bs.p[k] = scalars[k];
+    for (int k = 0; k < msets; k++) {
+      bs.p[k] = scalars[k];
+      bs.base[k] = set_base ? set_base[k] : 0u;
+    }
     fixed_bucketing(sc, p, bs, n, mdig | (table->mont_folded ? 0 : kDigMinForm), table, st, mark);
   } else {
     keys_dispatch(p.c, scalars[0], n, mdig, sc, st);
@@ -2189,9 +2205,9 @@ void msm_enqueue(MsmScratch& sc, const G1Affine* bases, const Fr* scalars, size_
 }
 
 void msm_enqueue_sets(MsmScratch& sc, const Fr* const* scalars, int sets, size_t n, bool mont, hipStream_t st,
-                      const MsmBaseTable* table) {
+                      const MsmBaseTable* table, const uint32_t* set_base) {
   if (!table) throw Error(NZCB_ERR_ARG, "msm sets: a table schedule");
-  msm_enqueue_impl(sc, nullptr, scalars, sets, n, mont, st, table);
+  msm_enqueue_impl(sc, nullptr, scalars, sets, n, mont, st, table, set_base);
 }
 
 // the fixed-base slots of set s combined on the host: W = 2^a sum_b 2^b R_b + sum_b 2^b C_b + C

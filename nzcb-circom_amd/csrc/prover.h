@@ -63,6 +63,19 @@ struct Prover {
   DevBuf<G1Affine> ltau;
   MsmBaseTable ltab;
   bool lcommit = false;
+  // The signal basis (csrc/sigbasis.h): A, B, C committed over the witness signals, against
+  // rows computed once per context. stab: the shifted-base table (Lagrange window) of 3 x
+  // sig_stride points, per set its sig_cnt[k] rows, the two blinding points, then infinities;
+  // sig_idx: the signal of each row. sigcommit is false when NZCB_SIGNAL_COMMIT=0, when the
+  // context has no Lagrange basis or when the expansion gave up (sig_note says why, logged with
+  // the lane's first logged proof).
+  MsmBaseTable stab;
+  DevBuf<uint32_t> sig_idx;
+  uint32_t sig_cnt[3] = {0, 0, 0};
+  size_t sig_stride = 0;
+  bool sigcommit = false;
+  std::string sig_note;
+  uint64_t sig_terms = 0;
   DevBuf<Fr> qm, ql, qr, qo, qc;  // [n coefs | 4n evals]
   DevBuf<Fr> sigma;               // 3 x [n | 4n]
   DevBuf<Fr> sig_h;               // 3 x n: sigma_k(w^i), contiguous (round 2)
@@ -90,6 +103,7 @@ struct Prover {
   DevBuf<Fr> wit;                 // nVars (witness + internal), Montgomery
   DevBuf<Fr> wtns_in;             // raw witness upload (normal form)
   DevBuf<Fr> A, B, C, Z;          // n (A, B, C: n + 2, the blinding scalars b_lo, b_hi at n, n + 1)
+  DevBuf<Fr> sig_scal;            // 3 x sig_stride: the signal basis's scalars, normal form (k_sig_stage)
   DevBuf<Fr> pol_a, pol_b, pol_c, pol_z;  // n+2 / n+3
   DevBuf<Fr> A4, B4, C4, Z4, T, Tz, t;  // 4n (A4..Z4: coset evaluations)
   DevBuf<Fr> bx_lo;               // 4096: beta x_lo[i] (the three-coset quotient's beta x)
@@ -157,8 +171,20 @@ struct Prover {
   // witness_on_device: `witness` is a device pointer (HBM-resident input, no PCIe copy)
   void prove(const uint8_t* witness, size_t n_witness, const uint8_t* blinding, uint8_t* proof_out,
              uint8_t* pub_out, bool witness_on_device = false);
+  // A, B and C's commitments of a witness (which need not satisfy the circuit) without a proof:
+  // 3 x 64 bytes, affine LEM. signal_basis: over the signal basis, else over the Lagrange basis
+  // in one schedule; NZCB_ERR_ARG when the context does not have that path (tests).
+  void debug_commit_abc(const uint8_t* witness, size_t n_witness, const uint8_t* blinding, bool signal_basis,
+                        uint8_t* out);
+  // set k's rows of the signal basis, affine LEM, from the table: sig_cnt[k] x 64 bytes and
+  // their signals
+  void debug_signal_rows(int set, uint8_t* rows_out, uint32_t* signals_out);
 
  private:
+  // blinding scalars and flags, the witness in Montgomery form, the additions, A, B, C (synchronises)
+  void load_witness(const uint8_t* witness, const uint8_t* blinding, bool witness_on_device);
+  void build_signal_basis(const Zkey& z);
+  bool sig_note_logged = false;
   hipStream_t st() const { return eng->stream; }
   void init_slots();
   void alloc_workspace();
@@ -171,7 +197,9 @@ struct Prover {
   void commit_start(int slot, const Fr* scalars, size_t len, const MsmBaseTable* tab = nullptr,
                     const G1Affine* bases = nullptr, bool on_main = false);
   G1Affine commit_finish(int slot);
-  void commit_start_abc(size_t len);  // A, B, C in one schedule (msm_enqueue_sets), main stream
+  // A, B, C in one schedule (msm_enqueue_sets), main stream; over the signal basis when the
+  // context has one and signal_basis is set, else over the Lagrange table (len = n + 2)
+  void commit_start_abc(size_t len, bool signal_basis);
   void commit_finish_abc(G1Affine& a, G1Affine& b, G1Affine& c);
   // np <= 8 evaluations p_j(x_j) (two launches, one host round trip)
   void eval_many(int np, const Fr* const* polys, const size_t* lens, const Fr* xs, Fr* out,

@@ -17,6 +17,7 @@
 #include <rocprofiler-sdk-roctx/roctx.h>
 #include "lagrange.h"
 #include "prover.h"
+#include "sigbasis.h"
 #include "transcript.h"
 
 #include <cstring>
@@ -122,6 +123,32 @@ __global__ void k_abc_tail(Fr* A, Fr* B, Fr* C, size_t n, const Fr* __restrict__
   B[n + 1] = bl[3];
   C[n] = bl[6];
   C[n + 1] = bl[5];
+}
+
+// The signal basis's scalars (Prover::stab, csrc/sigbasis.h): per set its signals' values, then
+// the set's two blinding scalars in k_abc_tail's order, then zeros up to stride; normal form (the
+// MSM's digit passes then take them as they are). wit is reduced and has variable 0 zeroed.
+__global__ void k_sig_stage(const uint32_t* __restrict__ idx, uint32_t stride, uint32_t c0, uint32_t c1, uint32_t c2,
+                            const Fr* __restrict__ wit, const Fr* __restrict__ bl, Fr* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)3 * stride) return;
+  const uint32_t set = (uint32_t)(i / stride), j = (uint32_t)(i - (size_t)set * stride);
+  const uint32_t cnt = set == 0 ? c0 : set == 1 ? c1 : c2;
+  Fr v = Fr::zero();
+  if (j < cnt) v = from_mont(wit[idx[i]]);
+  else if (j == cnt) v = from_mont(bl[2 + 2 * set]);
+  else if (j == cnt + 1) v = from_mont(bl[1 + 2 * set]);
+  out[i] = v;
+}
+
+// A, B, C over the witness signals (csrc/sigbasis.h); NZCB_SIGNAL_COMMIT=0 keeps the
+// Lagrange-basis schedule
+static bool signal_commit_enabled() {
+  static const bool v = [] {
+    const char* e = std::getenv("NZCB_SIGNAL_COMMIT");
+    return !e || std::atoi(e) != 0;
+  }();
+  return v;
 }
 
 // A, B, C in one MSM schedule (round 6); NZCB_ABC_SETS=0 commits them as three MSMs
@@ -1238,6 +1265,7 @@ Prover::Prover(const uint8_t* zkey_bytes, size_t len, int device) {
       NZ_HIP(hipMemcpyAsync(adds.p, sorted.data(), nAdditions * sizeof(AddRec), hipMemcpyHostToDevice, s));
     NZ_HIP(hipStreamSynchronize(s));
   }
+  if (lcommit && signal_commit_enabled() && abc_sets_enabled()) build_signal_basis(z);
   // 4n-th roots: w4^i = lo[i & 4095] * hi[i >> 12]
   Fr w4 = fr_root_of_unity(power + 2);
   size_t nlo = 4096, nhi = (n4 + 4095) / 4096;
@@ -1369,6 +1397,37 @@ Prover::Prover(const uint8_t* zkey_bytes, size_t len, int device) {
   NZ_HIP(hipStreamSynchronize(s));
 }
 
+// The signal basis, once per context (csrc/sigbasis.h): the rows over ltau, then one unfolded
+// table at the Lagrange window over the three sets' segments. The lanes alias it.
+void Prover::build_signal_basis(const Zkey& z) {
+  hipStream_t s = st();
+  if (z.additions.len < (uint64_t)nAdditions * 72 || z.amap.len < (uint64_t)nConstraints * 4 ||
+      z.bmap.len < (uint64_t)nConstraints * 4 || z.cmap.len < (uint64_t)nConstraints * 4) {
+    sig_note = "signal basis: the key's maps are shorter than its header says; A, B, C are committed from the "
+               "Lagrange basis";
+    return;
+  }
+  NZ_HIP(hipStreamSynchronize(s));  // ltau is complete
+  // msc[0] is sized for three sets of n + 6 points (init_slots)
+  SigBasis sb = sig_basis_build(eng->device, ltau.p, n, nWit, nVars, nConstraints, z.additions.p, nAdditions,
+                                z.amap.p, z.bmap.p, z.cmap.p, (size_t)n + 2);
+  sig_terms = sb.terms;
+  if (!sb.ok) {
+    sig_note = sb.note;
+    return;
+  }
+  for (int k = 0; k < 3; k++) sig_cnt[k] = sb.cnt[k];
+  sig_stride = sb.stride;
+  DevBuf<G1Affine> bases(sb.bases.size());
+  NZ_HIP(hipMemcpyAsync(bases.p, sb.bases.data(), sb.bases.size() * sizeof(G1Affine), hipMemcpyHostToDevice, s));
+  sig_idx.alloc(sb.idx.size());
+  NZ_HIP(hipMemcpyAsync(sig_idx.p, sb.idx.data(), sb.idx.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+  stab.build(bases.p, bases.n, lagrange_window(), s);
+  stab.sparse = lagrange_sparse();
+  NZ_HIP(hipStreamSynchronize(s));  // the host vectors and `bases` go with this scope
+  sigcommit = true;
+}
+
 void Prover::init_slots() {
   for (int i = 0; i < kSlots; i++) {
     msc[i].reset(new MsmScratch());
@@ -1397,6 +1456,7 @@ void Prover::alloc_workspace() {
   wit.alloc(nVars ? nVars : 1);
   wtns_in.alloc(nWit ? nWit : 1);
   A.alloc(n + 2); B.alloc(n + 2); C.alloc(n + 2); Z.alloc(n);
+  if (sigcommit) sig_scal.alloc(3 * sig_stride);
   pol_a.alloc(n + 2); pol_b.alloc(n + 2); pol_c.alloc(n + 2); pol_z.alloc(n + 3);
   // coset evaluations and the quotient: 3n under the three-coset quotient (T also holds
   // round 5's n + 6 Wxi numerator, t the 3n + 6 quotient coefficients), 4n otherwise
@@ -1450,6 +1510,15 @@ Prover::Prover(const Prover& pk, int lane) {
   ltab.q.alias(pk.ltab.q);
   ltab.n = pk.ltab.n; ltab.stride = pk.ltab.stride; ltab.c = pk.ltab.c; ltab.nw = pk.ltab.nw;
   ltab.sparse = pk.ltab.sparse;
+  sigcommit = pk.sigcommit;
+  sig_note = pk.sig_note;
+  sig_terms = pk.sig_terms;
+  sig_stride = pk.sig_stride;
+  for (int k = 0; k < 3; k++) sig_cnt[k] = pk.sig_cnt[k];
+  sig_idx.alias(pk.sig_idx);
+  stab.q.alias(pk.stab.q);
+  stab.n = pk.stab.n; stab.stride = pk.stab.stride; stab.c = pk.stab.c; stab.nw = pk.stab.nw;
+  stab.sparse = pk.stab.sparse;
   qm.alias(pk.qm); ql.alias(pk.ql); qr.alias(pk.qr); qo.alias(pk.qo); qc.alias(pk.qc);
   sigma.alias(pk.sigma); sig_h.alias(pk.sig_h); q_h.alias(pk.q_h); w_h.alias(pk.w_h); lagrange.alias(pk.lagrange);
   amap.alias(pk.amap); bmap.alias(pk.bmap); cmap.alias(pk.cmap); adds.alias(pk.adds);
@@ -1730,11 +1799,23 @@ G1Affine Prover::commit_finish(int slot) {
 
 // A, B and C's commitments in one schedule over the Lagrange table (msm.hip msm_enqueue_sets),
 // on the main stream, slot 0's scratch (sized for three sets, init_slots)
-void Prover::commit_start_abc(size_t len) {
+void Prover::commit_start_abc(size_t len, bool signal_basis) {
   roctxMarkA("mark: commit enqueue A, B, C");
   const Fr* sc[3] = {A.p, B.p, C.p};
   const size_t sp = prof_gpu ? span_begin(0, st()) : 0;
-  msm_enqueue_sets(*msc[0], sc, 3, len, true, st(), &ltab);
+  if (signal_basis && sigcommit) {
+    // over the signals: 3 x sig_stride normal-form scalars staged from wit, each set against its
+    // own segment of the signal table (csrc/sigbasis.h)
+    const uint32_t stride = (uint32_t)sig_stride;
+    hipLaunchKernelGGL(k_sig_stage, dim3(grid_for((size_t)3 * stride, kT, 1u << 30)), dim3(kT), 0, st(), sig_idx.p,
+                       stride, sig_cnt[0], sig_cnt[1], sig_cnt[2], wit.p, blind.p, sig_scal.p);
+    NZ_HIP(hipGetLastError());
+    const Fr* ss[3] = {sig_scal.p, sig_scal.p + stride, sig_scal.p + 2 * (size_t)stride};
+    const uint32_t base[3] = {0, stride, 2 * stride};
+    msm_enqueue_sets(*msc[0], ss, 3, stride, false, st(), &stab, base);
+  } else {
+    msm_enqueue_sets(*msc[0], sc, 3, len, true, st(), &ltab);
+  }
   if (prof_gpu) span_end(sp, st());
   roctxMarkA("mark: commit enqueued A, B, C");
 }
@@ -1748,6 +1829,43 @@ void Prover::commit_finish_abc(G1Affine& a, G1Affine& b, G1Affine& c) {
   b = xyzz_to_affine(r[1]);
   c = xyzz_to_affine(r[2]);
   msm_ms += ms_since(t0);
+}
+
+void Prover::debug_commit_abc(const uint8_t* witness, size_t n_witness, const uint8_t* blinding, bool signal_basis,
+                              uint8_t* out) {
+  if (!witness || !blinding || !out || n_witness != nWit) throw Error(NZCB_ERR_ARG, "commit A, B, C: bad argument");
+  if (!lcommit || !shards.empty() || split_send || msc[0]->max_lsets < 3)
+    throw Error(NZCB_ERR_ARG, "commit A, B, C: the context does not commit them in one schedule");
+  if (signal_basis && !sigcommit) throw Error(NZCB_ERR_ARG, "commit A, B, C: the context has no signal basis");
+  NZ_HIP(hipSetDevice(eng->device));
+  if (side_done) NZ_HIP(hipEventSynchronize(side_done));
+  load_witness(witness, blinding, false);
+  hipLaunchKernelGGL(k_abc_tail, dim3(1), dim3(64), 0, st(), A.p, B.p, C.p, (size_t)n, blind.p);
+  NZ_HIP(hipGetLastError());
+  commit_start_abc(n + 2, signal_basis);
+  G1Affine p[3];
+  commit_finish_abc(p[0], p[1], p[2]);
+  std::memcpy(out, p, sizeof p);
+}
+
+void Prover::debug_signal_rows(int set, uint8_t* rows_out, uint32_t* signals_out) {
+  if (set < 0 || set > 2 || !sigcommit) throw Error(NZCB_ERR_ARG, "signal rows: no such set or no signal basis");
+  NZ_HIP(hipSetDevice(eng->device));
+  const uint32_t cnt = sig_cnt[set];
+  if (!cnt) return;
+  if (!rows_out || !signals_out) throw Error(NZCB_ERR_ARG, "null argument");
+  // the table's first row holds the points themselves with coordinates x 2^261 (MsmBaseTable)
+  std::vector<G1Affine> q(cnt);
+  NZ_HIP(hipMemcpy(q.data(), stab.q.p + (size_t)set * sig_stride, cnt * sizeof(G1Affine), hipMemcpyDeviceToHost));
+  NZ_HIP(hipMemcpy(signals_out, sig_idx.p + (size_t)set * sig_stride, cnt * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  Fq thirty_two = Fq::zero();
+  thirty_two.v[0] = 32;
+  const Fq k = inverse(to_mont(thirty_two));  // 2^-5, Montgomery
+  for (uint32_t i = 0; i < cnt; i++) {
+    q[i].x = q[i].x * k;
+    q[i].y = q[i].y * k;
+  }
+  std::memcpy(rows_out, q.data(), cnt * sizeof(G1Affine));
 }
 
 void Prover::set_msm_split(int world, size_t own_points, size_t own_lagrange, nzcb_msm_send_fn send,
@@ -1898,30 +2016,8 @@ Fr random_fr() {
 }
 }  // namespace
 
-void Prover::prove(const uint8_t* witness, size_t n_witness, const uint8_t* blinding, uint8_t* proof_out,
-                   uint8_t* pub_out, bool witness_on_device) {
-  if (n_witness != nWit) {
-    throw Error(NZCB_ERR_WITNESS_LEN, "Invalid witness length. Circuit: " + std::to_string(nVars) +
-                                          ", witness: " + std::to_string(n_witness) + ", " +
-                                          std::to_string(nAdditions));
-  }
-  NZ_HIP(hipSetDevice(eng->device));
+void Prover::load_witness(const uint8_t* witness, const uint8_t* blinding, bool witness_on_device) {
   hipStream_t s = st();
-  msm_ms = ntt_ms = 0;
-  spans_used = 0;
-  // a previous proof that failed in round 2 may have left the side stream's NTTs running
-  // on this lane's buffers (blind, A, B, C)
-  if (side_done) NZ_HIP(hipEventSynchronize(side_done));
-  // which lane proves (rocprofv3 --marker-trace; tools/lane_speeds.py: lanes differ in speed by
-  // the hardware queues their streams landed on, profiles/r6_drain_queues.txt)
-  static const char* kLaneMark[17] = {"lane 0", "lane 1", "lane 2", "lane 3", "lane 4", "lane 5", "lane 6", "lane 7",
-                                      "lane 8", "lane 9", "lane 10", "lane 11", "lane 12", "lane 13", "lane 14",
-                                      "lane 15", "lane 16"};
-  roctxMarkA(kLaneMark[lane_id < 16 ? lane_id : 16]);
-  RoctxPhases ranges("plonk_prove");
-  ranges.next("witness: calculateAdditions + buildABC");
-  auto T0 = std::chrono::steady_clock::now();
-  auto lg = [&](const std::string& m) { if (log) log(m); };
   // blinding scalars b1..b11 (Montgomery); index 0 unused
   Fr bl[13];
   bl[0] = Fr::zero();
@@ -1931,8 +2027,6 @@ void Prover::prove(const uint8_t* witness, size_t n_witness, const uint8_t* blin
   // explicit bytes (all zero included)
   for (int i = 1; i <= 11; i++) bl[i] = blinding ? fr_from_le_normal(blinding + 32 * (i - 1)) : random_fr();
   NZ_HIP(hipMemcpyAsync(blind.p, bl, sizeof(bl), hipMemcpyHostToDevice, s));
-
-  lg("Reading Wtns");
   const Fr* wsrc = (const Fr*)witness;
   if (!witness_on_device) {
     NZ_HIP(hipMemcpyAsync(wtns_in.p, witness, (size_t)nWit * 32, hipMemcpyHostToDevice, s));
@@ -1959,6 +2053,38 @@ void Prover::prove(const uint8_t* witness, size_t n_witness, const uint8_t* blin
                      top_host + mb_apub, top_host + mb_pubw);
   NZ_HIP(hipGetLastError());
   NZ_HIP(hipStreamSynchronize(s));
+}
+
+void Prover::prove(const uint8_t* witness, size_t n_witness, const uint8_t* blinding, uint8_t* proof_out,
+                   uint8_t* pub_out, bool witness_on_device) {
+  if (n_witness != nWit) {
+    throw Error(NZCB_ERR_WITNESS_LEN, "Invalid witness length. Circuit: " + std::to_string(nVars) +
+                                          ", witness: " + std::to_string(n_witness) + ", " +
+                                          std::to_string(nAdditions));
+  }
+  NZ_HIP(hipSetDevice(eng->device));
+  hipStream_t s = st();
+  msm_ms = ntt_ms = 0;
+  spans_used = 0;
+  // a previous proof that failed in round 2 may have left the side stream's NTTs running
+  // on this lane's buffers (blind, A, B, C)
+  if (side_done) NZ_HIP(hipEventSynchronize(side_done));
+  // which lane proves (rocprofv3 --marker-trace; tools/lane_speeds.py: lanes differ in speed by
+  // the hardware queues their streams landed on, profiles/r6_drain_queues.txt)
+  static const char* kLaneMark[17] = {"lane 0", "lane 1", "lane 2", "lane 3", "lane 4", "lane 5", "lane 6", "lane 7",
+                                      "lane 8", "lane 9", "lane 10", "lane 11", "lane 12", "lane 13", "lane 14",
+                                      "lane 15", "lane 16"};
+  roctxMarkA(kLaneMark[lane_id < 16 ? lane_id : 16]);
+  RoctxPhases ranges("plonk_prove");
+  ranges.next("witness: calculateAdditions + buildABC");
+  auto T0 = std::chrono::steady_clock::now();
+  auto lg = [&](const std::string& m) { if (log) log(m); };
+  if (!sig_note.empty() && !sig_note_logged && log) {  // the signal basis gave up at setup (csrc/sigbasis.h)
+    lg(sig_note);
+    sig_note_logged = true;
+  }
+  lg("Reading Wtns");
+  load_witness(witness, blinding, witness_on_device);
   tm[1] = ms_since(T0);
 
   // ---------------- round 1 ----------------
@@ -1983,7 +2109,7 @@ void Prover::prove(const uint8_t* witness, size_t n_witness, const uint8_t* blin
         lg("multiexp A");  // snarkjs's logger lines, one per commitment
         lg("multiexp B");
         lg("multiexp C");
-        commit_start_abc(n + 2);
+        commit_start_abc(n + 2, true);
       } else {
       lg("multiexp A");
       commit_start(0, A.p, n + 2, &ltab, ltau.p);

@@ -61,6 +61,7 @@ EXPORTED_SYMBOLS = [
     "nzcb_groth16_setup", "nzcb_groth16_setup_file", "nzcb_groth16_contribute", "nzcb_groth16_contribute_file",
     "nzcb_groth16_vk_to_json", "nzcb_groth16_vk_to_json_file", "nzcb_engine_groth16_rows",
     "nzcb_debug_groth16_schedule", "nzcb_debug_groth16_timings",
+    "nzcb_debug_signal_basis_cap", "nzcb_debug_signal_basis_info", "nzcb_debug_commit_abc", "nzcb_debug_signal_rows",
 ]
 
 NZCB_FAULT_QUOTIENT = 1  # include/nzcb_internal.h
@@ -96,6 +97,13 @@ def lagrange_commit_enabled() -> bool:
         return True
     m = re.match(r"\s*[+-]?\d+", e)   # as C's atoi: the leading integer, 0 without one
     return bool(m) and int(m.group()) != 0
+
+
+def signal_basis_cap(per_constraint: int = -1) -> int:
+    """The signal basis's expansion gives up past per_constraint * 3 * nConstraints terms, for the
+    contexts created after this call (nzcb_debug_signal_basis_cap; < 0 restores the library's 64).
+    Returns the previous value."""
+    return load().nzcb_debug_signal_basis_cap(per_constraint)
 
 
 def guard_check(device: int = -1) -> int:
@@ -357,6 +365,10 @@ def load(path: str | None = None):
                                              ctypes.c_uint64, POINTER(c_uint32), u8p, u8p, POINTER(_Err)]),
         "nzcb_debug_groth16_schedule": (c_int, [c_int, c_int, POINTER(c_int), POINTER(c_int)]),
         "nzcb_debug_groth16_timings": (c_int, [POINTER(c_double), c_int]),
+        "nzcb_debug_signal_basis_cap": (c_int, [c_int]),
+        "nzcb_debug_signal_basis_info": (c_int, [c_void_p, POINTER(c_uint64)]),
+        "nzcb_debug_commit_abc": (c_int, [c_void_p, u8p, c_size_t, u8p, c_int, u8p, POINTER(_Err)]),
+        "nzcb_debug_signal_rows": (c_int, [c_void_p, c_int, u8p, POINTER(c_uint32), c_size_t, POINTER(_Err)]),
     }
     lib.missing_symbols = []
     for name, (res, args) in sigs.items():
@@ -999,6 +1011,39 @@ class ProverContext:
         (NZCB_FAULT_LANE_ALLOC: tests of the rollback); 0 clears it."""
         if self.lib.nzcb_debug_inject_fault(self.h, kind) != 0:
             raise ValueError(f"bad fault kind {kind}")
+
+    def signal_basis_info(self) -> dict:
+        """The context's signal basis (include/nzcb_internal.h nzcb_debug_signal_basis_info):
+        whether A, B, C are committed over it, the rows per set, the points per set in the table,
+        the expansion's terms and the table's bytes."""
+        out = (c_uint64 * 7)()
+        self.lib.nzcb_debug_signal_basis_info(self.h, out)
+        return {"on": bool(out[0]), "rows": [int(out[1]), int(out[2]), int(out[3])], "stride": int(out[4]),
+                "terms": int(out[5]), "table_bytes": int(out[6])}
+
+    def commit_abc(self, witness_le: bytes, blinding: bytes, signal_basis: bool):
+        """A, B and C's commitments of a witness (32-byte LE normal-form values, which need not
+        satisfy the circuit) without a proof, over the signal basis or over the Lagrange basis
+        (nzcb_debug_commit_abc): three 64-byte affine LEM points."""
+        if len(blinding) != BLINDING_BYTES:
+            raise ValueError("blinding must be 11 x 32 bytes")
+        out = _out(192)
+        err = _Err()
+        _check(self.lib.nzcb_debug_commit_abc(self.h, _buf(witness_le), len(witness_le) // 32, _buf(blinding),
+                                              int(signal_basis), out, ctypes.byref(err)), err)
+        b = bytes(out)
+        return b[:64], b[64:128], b[128:]
+
+    def signal_rows(self, k: int) -> dict:
+        """Set k's rows of the signal basis (0, 1, 2 = A, B, C; nzcb_debug_signal_rows): signal ->
+        64-byte affine LEM row. A signal that is not a key has no row in the set."""
+        cnt = self.signal_basis_info()["rows"][k]
+        rows = _out(64 * cnt)
+        sig = (c_uint32 * max(cnt, 1))()
+        err = _Err()
+        _check(self.lib.nzcb_debug_signal_rows(self.h, k, rows, sig, cnt, ctypes.byref(err)), err)
+        b = bytes(rows)
+        return {int(sig[i]): b[64 * i:64 * i + 64] for i in range(cnt)}
 
     def kernel_stats(self, enable: int = -1):
         """MSM bucket-accumulation kernel timing: (ms, launches, points, entries); enable 1/0 resets."""
