@@ -77,6 +77,50 @@ int nzcb_debug_signal_rows(nzcb_ctx* ctx, int set, uint8_t* rows_out, uint32_t* 
  * 1..28; 9 out). Synchronous; count <= 2^24. */
 int nzcb_debug_f29(int device, int op, const uint32_t* in, size_t count, uint32_t* out, nzcb_err* err);
 
+/* ---- The prover's round 2-5 kernels alone (csrc/prover.hip) ---------------------------------- */
+/* Each entry launches the kernels and host helpers the prover launches for that step, on `device`
+ * with a stream and buffers of its own, synchronously, and needs no context. Field values are
+ * 32-byte LE Montgomery words ("LEM", as nzcb_engine_ntt) in host memory and canonical (below r;
+ * NZCB_ERR_ARG otherwise), so a caller chooses the raw words the kernels load. Arrays of several
+ * columns are column-major ([k][n]: column k at k * n). At most 2^26 elements per column. */
+/* Round 2's grand product (k_perm_tile, k_perm_factors, k_apply_tiles): z_out[i] = prod_{k<i} N_k
+ * prod_{k>=i} D_k / prod D over n >= 1 elements, with N_i = (a_i + beta x_i + gamma)(b_i + k1 beta
+ * x_i + gamma)(c_i + k2 beta x_i + gamma) and D_i the same over sigma: (a_i + beta s1_i + gamma)(..)
+ * (..). x stands in for the prover's table of w^i and may hold any field elements. totals_out: 2
+ * words, prod N and prod D as the kernels form them, both times the same power of two (the
+ * prover compares them; this entry does not). The k beta x_i are formed by additions when (k1,
+ * k2) = (2, 3) and generic_k = 0, else by their own products. prod D = 0 has no defined result. */
+int nzcb_debug_grand_product(int device, const uint8_t* abc /* [3][n] */, const uint8_t* sigma /* [3][n] */,
+                             const uint8_t* x /* [n] */, size_t n, const uint8_t* beta, const uint8_t* gamma,
+                             const uint8_t* k1, const uint8_t* k2, int generic_k, uint8_t* z_out /* [n] */,
+                             uint8_t* totals_out /* [2] */, nzcb_err* err);
+/* Round 5's divPol1 (the power tables for d, k_lin_tile, k_tile_heads, k_div_check): q_out[i] =
+ * p[i + 1] + d q_out[i + 1] for i < m - 1, q_out[m - 1] = 0, m >= 2. *divides_out = 1 when p[0] -
+ * p0_adjust = -d q_out[0], else 0: the check that makes a proof fail with NZCB_ERR_DIVPOL. */
+int nzcb_debug_div_pol1(int device, const uint8_t* p /* [m] */, size_t m, const uint8_t* d, const uint8_t* p0_adjust,
+                        uint8_t* q_out /* [m] */, int* divides_out, nzcb_err* err);
+/* Round 4's evaluations (k_eval_pows, k_eval_multi, k_eval_sum): out[j] = polys[j](xs[j]) for np
+ * = 1 or 7 polynomials (the two forms the prover runs) of lens[j] >= 1 coefficients each. */
+int nzcb_debug_eval_many(int device, int np, const uint8_t* const* polys, const size_t* lens,
+                         const uint8_t* xs /* [np] */, uint8_t* out /* [np] */, nzcb_err* err);
+/* Round 3's quotient numerator at P points of the domain n = 2^power (power >= 2), point by point:
+ *   N = qm a b + ql a + qr b + qo c + qc - sum_j L_j apub_j
+ *       + alpha [(a + beta x + gamma)(b + k1 beta x + gamma)(c + k2 beta x + gamma) z
+ *                - (a + beta s1 + gamma)(b + beta s2 + gamma)(c + beta s3 + gamma) z(w x)]
+ *       + alpha^2 (z - 1) L_0
+ * in the kernels' own point order, with w4 the 4n-th root of unity and g = 5. three = 1: P = 3n,
+ * index j n + m is x = g w4^(4m + j) and z(w x) is z at j n + (m + 1 mod n); t_out = N
+ * (k_beta_xlo when (k1, k2) = (2, 3), k_quotient_coset29<true>; npub <= 8, NZCB_ERR_ARG past it).
+ * three = 0: P = 4n, x_i = g w4^i, z(w x) is z at (i + 4) mod 4n; t_out = N / (x^n - 1)
+ * (k_quotient_coset29<false> for npub <= 8, the 8x32 k_quotient_coset past it). Inputs are
+ * unscaled: the entry applies the context's exponent pre-scaling and builds the point tables.
+ * l holds max(npub, 1) columns (L_0 is read with npub = 0 too). */
+int nzcb_debug_quotient(int device, int power, int three, uint32_t npub, const uint8_t* abcz /* [4][P] */,
+                        const uint8_t* q /* [5][P] */, const uint8_t* s /* [3][P] */,
+                        const uint8_t* l /* [max(npub, 1)][P] */, const uint8_t* apub /* [npub] */, const uint8_t* beta,
+                        const uint8_t* gamma, const uint8_t* alpha, const uint8_t* k1, const uint8_t* k2,
+                        uint8_t* t_out /* [P] */, nzcb_err* err);
+
 /* ---- Synthetic circuit + setup ------- */
 /* Builds the seeded synthetic circuit of oracle/synth.py and its snarkjs-0.4
  * PLONK zkey with trapdoor tau (32-byte LE normal) on `device`. Buffers are

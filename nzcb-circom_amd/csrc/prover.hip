@@ -15,6 +15,7 @@
 //   * divPol1          -> suffix linear-recurrence scan y_i = x_i + d*y_{i+1}
 //   * evalPol (Horner) -> chunked Horner * x^(chunk start) + tree sum
 #include <rocprofiler-sdk-roctx/roctx.h>
+#include "devcall.h"
 #include "lagrange.h"
 #include "prover.h"
 #include "sigbasis.h"
@@ -549,7 +550,8 @@ k_apply_tiles(Fr* __restrict__ x, size_t m, const Fr* __restrict__ F, Fr inv_d) 
 // the scan is of additions: two products per thread instead of two per Kogge-Stone step
 // (round 3's multiplicative scan, 16 products per thread). Two passes: kWrite = false writes
 // the tile heads (c = 0), which a small scan turns into the true carries; kWrite = true
-// recomputes the tile with its carry and writes y. d = 0 (y = x) works with Pinv = 0.
+// recomputes the tile with its carry and writes y. d = 0 (y = x): P[t] = 0 for t > 0, so every
+// sum that Pinv[t > 0] multiplies is 0 and its value there (inverse(0) = 0) does not matter.
 struct LinTab {
   Fr P[kT + 1];     // d^(kPer t)
   Fr Pinv[kT + 1];  // d^(-kPer t) (0 for t > 0 when d = 0)
@@ -1068,6 +1070,218 @@ static Fr fr_small(uint64_t k) {
   return to_mont(x);
 }
 
+// ----------------------------------------------------------------------------
+// rounds 2-5: kernel arguments, tables and launches, shared by Prover and the kernel-level
+// entries at the end of this file (include/nzcb_internal.h nzcb_debug_grand_product, ...)
+// ----------------------------------------------------------------------------
+static bool k_is_23(const Fr& k1, const Fr& k2) { return k1 == fr_small(2) && k2 == fr_small(3); }
+
+// round 2's kernel arguments; generic_k: k1 beta w and k2 beta w by their own Shoup products
+// even when k1, k2 = 2, 3
+static PermArgs perm_args(const Fr& beta, const Fr& gamma, const Fr& k1, const Fr& k2, bool generic_k) {
+  PermArgs pa;
+  shoup_pair(beta, pa.beta, pa.beta_s);
+  shoup_pair(k1 * beta, pa.k1beta, pa.k1beta_s);
+  shoup_pair(k2 * beta, pa.k2beta, pa.k2beta_s);
+  pa.gamma256 = f29_exp(gamma, 0);
+  pa.k23 = !generic_k && k_is_23(k1, k2) ? 1 : 0;
+  return pa;
+}
+
+static size_t perm_tiles(size_t n) { return (n + kTileN - 1) / kTileN; }
+
+// The grand product up to its last factor: the tile-local Z, then per tile the numerator and
+// denominator totals and the factors F_T in scan (3 x perm_tiles(n) words), prod num and prod
+// den in totals[0..2) (coherent host memory, valid once s has been synchronised)
+static void perm_launch(const Fr* A, const Fr* B, const Fr* C, const Fr* sig_h, size_t n, const Fr* w_h,
+                        const PermArgs& pa, Fr* Z, Fr* scan, Fr* totals, hipStream_t s) {
+  const size_t ntiles = perm_tiles(n);
+  if (ntiles > 1024 * 64) throw Error(NZCB_ERR_INTERNAL, "round 2: domain too large for the tile factors");
+  Fr* ntot = scan;  // per tile: numerator / denominator totals, then the factors F_T
+  Fr* dtot = ntot + ntiles;
+  Fr* fac = dtot + ntiles;
+  hipLaunchKernelGGL(k_perm_tile, dim3((unsigned)ntiles), dim3(kT), 0, s, A, B, C, sig_h, n, w_h, pa, Z, ntot, dtot);
+  hipLaunchKernelGGL(k_perm_factors, dim3(1), dim3(1024), 0, s, (const Fr*)ntot, (const Fr*)dtot, (int)ntiles, fac,
+                     totals);
+  NZ_HIP(hipGetLastError());
+}
+
+// ... and the last: Z[i] *= F_T / prod den
+static void perm_apply(Fr* Z, size_t n, const Fr* scan, const Fr& den_total, hipStream_t s) {
+  const size_t ntiles = perm_tiles(n);
+  hipLaunchKernelGGL(k_apply_tiles, dim3((unsigned)ntiles), dim3(kT), 0, s, Z, n, scan + 2 * ntiles,
+                     inverse(den_total));
+  NZ_HIP(hipGetLastError());
+}
+
+// round 3's kernel arguments: the 8x32 kernel's and the 9x29 kernels'
+static QArgs quot_args(const Fr& beta, const Fr& gamma, const Fr& alpha, const Fr& k1, const Fr& k2,
+                       const Fr (&zh_inv)[4]) {
+  QArgs q;
+  q.beta = beta;
+  q.gamma = gamma;
+  q.alpha = alpha;
+  q.alpha2 = alpha * alpha;
+  q.bk1 = beta * k1;
+  q.bk2 = beta * k2;
+  for (int k = 0; k < 4; k++) q.zhinv[k] = zh_inv[k];
+  return q;
+}
+static QArgs29 quot_args29(const Fr& beta, const Fr& gamma, const Fr& alpha, const Fr& k1, const Fr& k2,
+                           const Fr (&zh_inv)[4]) {
+  QArgs29 q29;
+  q29.beta = f29_exp(beta, 5);
+  q29.k23 = k_is_23(k1, k2) ? 1 : 0;
+  q29.bk1 = f29_exp(beta * k1, 5);
+  q29.bk2 = f29_exp(beta * k2, 5);
+  q29.alpha2 = f29_exp(alpha * alpha, 5);
+  for (int k = 0; k < 4; k++) q29.zhinv[k] = f29_exp(zh_inv[k], 5);  // (three cosets: unread, 1/Z_H is in itw3)
+  q29.gamma = f29_exp(gamma, 0);
+  q29.negone = f29_exp(neg(Fr::one()), 0);
+  q29.alpha = f29_exp(alpha, 20);
+  return q29;
+}
+
+static void root_table(DevBuf<Fr>& out, size_t cnt, const Fr& base, const Fr& scale, hipStream_t s) {
+  out.alloc(cnt);
+  hipLaunchKernelGGL(k_root_table, dim3(grid_for(cnt, kT)), dim3(kT), 0, s, out.p, base, scale, cnt);
+  NZ_HIP(hipGetLastError());
+}
+
+// The quotient's point tables for the domain 2^power: x_lo[i] = g w4^i (i < 4096) and root_hi[k] =
+// w4^(4096 k), so x_i = x_lo[i & 4095] root_hi[i >> 12] on the coset g <w4>, g = 5 (the Fr
+// multiplicative generator, ffjavascript's nqr), and zh_inv[k] = 1 / Z_H(x_i) = 1 / (g^n w4^(i n)
+// - 1) for i mod 4 = k
+static void quot_x_tables(int power, DevBuf<Fr>& x_lo, DevBuf<Fr>& root_hi, Fr (&zh_inv)[4], hipStream_t s) {
+  const size_t n = (size_t)1 << power, n4 = 4 * n;
+  const Fr w4 = fr_root_of_unity(power + 2), g = fr_small(5), one = Fr::one();
+  root_table(x_lo, 4096, w4, g, s);
+  root_table(root_hi, (n4 + 4095) / 4096, pow_u64(w4, 4096), one, s);
+  Fr gn = pow_u64(g, n), w4n = pow_u64(w4, n), p = gn;
+  for (int k = 0; k < 4; k++) {
+    zh_inv[k] = inverse(p - one);
+    p = p * w4n;
+  }
+}
+
+// exponent pre-scaling of the 29-bit quotient (k_quotient_coset29): cq = Qm..Qc (5 x npts), cl =
+// L_j (nl x npts), x_lo the low point table
+static void quot29_prescale(Fr* cq, Fr* cl, uint32_t nl, size_t npts, Fr* x_lo, hipStream_t s) {
+  auto scale = [&](Fr* p, size_t m, int e) {
+    hipLaunchKernelGGL(k_dbl_pow, dim3(grid_for(m, kT, 1u << 30)), dim3(kT), 0, s, p, m, e);
+  };
+  scale(cq, npts, 10);             // qm
+  scale(cq + npts, 3 * npts, 5);   // ql, qr, qo
+  scale(cl, (size_t)nl * npts, 5); // L_j
+  scale(x_lo, 4096, 5);            // g w4^j
+  NZ_HIP(hipGetLastError());
+}
+
+// Round 3's quotient kernel over 3n (three: the three-coset form, N(x) itself) or 4n points:
+// the 9x29 kernels up to kQ29MaxPub public inputs (over arrays that quot29_prescale scaled),
+// else the 8x32 kernel (unscaled arrays; never with three). bx_lo: 4096 words, written here
+// (three with k1, k2 = 2, 3).
+static void quot_launch(bool three, const Fr* A4, const Fr* B4, const Fr* C4, const Fr* Z4, const Fr* cq, const Fr* cs,
+                        const Fr* cl, uint32_t npub, const Fr* Apub, size_t n, const Fr* x_lo, const Fr* root_hi,
+                        Fr* bx_lo, const Fr& beta, const Fr& gamma, const Fr& alpha, const Fr& k1, const Fr& k2,
+                        const Fr (&zh_inv)[4], Fr* T, hipStream_t s) {
+  if (three && npub > kQ29MaxPub) throw Error(NZCB_ERR_INTERNAL, "round 3: three cosets with too many public inputs");
+  if (npub > kQ29MaxPub) {
+    const QArgs q = quot_args(beta, gamma, alpha, k1, k2, zh_inv);
+    hipLaunchKernelGGL(k_quotient_coset, dim3(grid_for(4 * n, kT, 1u << 30)), dim3(kT), 0, s, A4, B4, C4, Z4, cq, cs,
+                       cl, npub, Apub, n, x_lo, root_hi, q, T);
+  } else {
+    const QArgs29 q29 = quot_args29(beta, gamma, alpha, k1, k2, zh_inv);
+    if (three) {
+      if (q29.k23)
+        hipLaunchKernelGGL(k_beta_xlo, dim3(grid_for(4096, kT)), dim3(kT), 0, s, x_lo, q29.beta, (size_t)4096, bx_lo);
+      hipLaunchKernelGGL((k_quotient_coset29<true>), dim3(grid_for(3 * n, kT, 1u << 30)), dim3(kT), 0, s, A4, B4, C4,
+                         Z4, cq, cs, cl, npub, Apub, n, x_lo, root_hi, (const Fr*)bx_lo, q29, T);
+    } else {
+      hipLaunchKernelGGL((k_quotient_coset29<false>), dim3(grid_for(4 * n, kT, 1u << 30)), dim3(kT), 0, s, A4, B4, C4,
+                         Z4, cq, cs, cl, npub, Apub, n, x_lo, root_hi, (const Fr*)nullptr, q29, T);
+    }
+  }
+  NZ_HIP(hipGetLastError());
+}
+
+// Round 4's evaluation set of np polynomials at their points, and its workgroup count
+static EvalSet eval_set(int np, const Fr* const* polys, const size_t* lens, const Fr* xs, size_t* nblocks_out) {
+  if (np < 1 || np > kEvalMax) throw Error(NZCB_ERR_INTERNAL, "eval_many: bad count");
+  EvalSet es{};
+  size_t maxlen = 0;
+  for (int j = 0; j < np; j++) {
+    es.p[j] = polys[j];
+    es.len[j] = lens[j];
+    es.x[j] = xs[j];
+    es.x29[j] = fr29_operand(xs[j]);
+    es.y29[j] = fr29_operand(pow_u64(xs[j], kT));
+    es.x4096[j] = pow_u64(xs[j], (uint64_t)kT * kEvalChunk2);
+    maxlen = std::max(maxlen, lens[j]);
+  }
+  es.np = np;
+  const size_t nblocks = (maxlen + (size_t)kT * kEvalChunk2 - 1) / ((size_t)kT * kEvalChunk2);
+  if (nblocks > ((size_t)1 << kEvalBits)) throw Error(NZCB_ERR_INTERNAL, "eval_many: polynomial too long");
+  es.nbits = 1;
+  while (((size_t)1 << es.nbits) < nblocks) es.nbits++;
+  *nblocks_out = nblocks;
+  return es;
+}
+
+// part: np x nblocks partial sums; pw: kEvalMax x kT; pw2: kEvalMax x kEvalBits; out: np results
+// in coherent host memory, valid once s has been synchronised
+static void eval_launch(const EvalSet& es, size_t nblocks, Fr* part, F29* pw, Fr* pw2, Fr* out, hipStream_t s) {
+  const int np = es.np;
+  hipLaunchKernelGGL(k_eval_pows, dim3((unsigned)np), dim3(kT), 0, s, es, pw, pw2);
+  if (np == 7)
+    hipLaunchKernelGGL(k_eval_multi<7>, dim3((unsigned)nblocks), dim3(kT), 0, s, es, (const F29*)pw, (const Fr*)pw2,
+                       part, (int)nblocks);
+  else if (np == 1)
+    hipLaunchKernelGGL(k_eval_multi<1>, dim3((unsigned)nblocks), dim3(kT), 0, s, es, (const F29*)pw, (const Fr*)pw2,
+                       part, (int)nblocks);
+  else
+    throw Error(NZCB_ERR_INTERNAL, "eval_many: 1 or 7 evaluations");
+  NZ_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_eval_sum, dim3(np), dim3(kT), 0, s, (const Fr*)part, (int)nblocks, out);
+  NZ_HIP(hipGetLastError());
+}
+
+// divPol1's power tables for d: the LinTab in t (host; it must live until s has passed the copy)
+// and at dev, and the tile powers Q[T], T < qn, then Qinv[T], T < qn, at q
+static void lin_tables_build(LinTab& t, const Fr& d, LinTab* dev, Fr* q, int qn, hipStream_t s) {
+  t.dp[0] = Fr::one();
+  for (int j = 1; j <= kPer; j++) t.dp[j] = t.dp[j - 1] * d;
+  const Fr dk = t.dp[kPer], dki = inverse(dk);  // inverse(0) = 0: Pinv = 0 past t = 0
+  t.P[0] = t.Pinv[0] = Fr::one();
+  for (int i = 1; i <= kT; i++) {
+    t.P[i] = t.P[i - 1] * dk;
+    t.Pinv[i] = t.Pinv[i - 1] * dki;
+  }
+  NZ_HIP(hipMemcpyAsync(dev, &t, sizeof(LinTab), hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(k_pow_tiles, dim3((qn + 255) / 256), dim3(256), 0, s, t.P[kT], t.Pinv[kT], qn, q, q + qn);
+  NZ_HIP(hipGetLastError());
+}
+
+static size_t lin_tiles(size_t m) { return (m + kTileN - 1) / kTileN; }
+
+// dst = divPol1(src, d) over m coefficients by the tables of lin_tables_build (q: Q then Qinv, qn
+// > lin_tiles(m) each); heads: lin_tiles(m) + 1 words; the check sets flag_bit in *flags and
+// copies the word to *mb_flags (coherent host memory)
+static void div_pol1_launch(const Fr* src, size_t m, const LinTab* lt, const Fr& d, const Fr* q, size_t qn, Fr* heads,
+                            const Fr& p0_adjust, Fr* dst, uint32_t* flags, uint32_t flag_bit, uint32_t* mb_flags,
+                            hipStream_t s) {
+  const size_t ntiles = lin_tiles(m);
+  if (ntiles + 1 > qn) throw Error(NZCB_ERR_INTERNAL, "divPol1: more tiles than its power tables");
+  hipLaunchKernelGGL(k_lin_tile<false>, dim3((unsigned)ntiles), dim3(kT), 0, s, src, m, lt, (const Fr*)nullptr, heads);
+  // true heads: H_T = h_T + d^kTileN H_(T+1), by the tile power tables (additions)
+  hipLaunchKernelGGL(k_tile_heads, dim3(1), dim3(1024), 0, s, heads, (int)ntiles, q, q + qn);
+  NZ_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_lin_tile<true>, dim3((unsigned)ntiles), dim3(kT), 0, s, src, m, lt, (const Fr*)heads, dst);
+  hipLaunchKernelGGL(k_div_check, dim3(1), dim3(64), 0, s, src, p0_adjust, (const Fr*)dst, d, flags, flag_bit,
+                     mb_flags);
+  NZ_HIP(hipGetLastError());
+}
+
 Prover::~Prover() {
   for (int i = 0; i < kSlots; i++) {
     if (aux[i]) {
@@ -1270,20 +1484,15 @@ Prover::Prover(const uint8_t* zkey_bytes, size_t len, int device) {
   Fr w4 = fr_root_of_unity(power + 2);
   size_t nlo = 4096, nhi = (n4 + 4095) / 4096;
   const Fr one = Fr::one();
-  auto table = [&](DevBuf<Fr>& out, size_t cnt, const Fr& base, const Fr& scale) {
-    out.alloc(cnt);
-    hipLaunchKernelGGL(k_root_table, dim3(grid_for(cnt, kT)), dim3(kT), 0, s, out.p, base, scale, cnt);
-    NZ_HIP(hipGetLastError());
-  };
+  auto table = [&](DevBuf<Fr>& out, size_t cnt, const Fr& base, const Fr& scale) { root_table(out, cnt, base, scale, s); };
   table(root_lo, nlo, w4, one);
-  table(root_hi, nhi, pow_u64(w4, 4096), one);
+  // coset g*<w4>, g = 5 (the Fr multiplicative generator, ffjavascript's nqr): x_i = g*w4^i,
+  // g^j and g^-j for coset (un)scaling, and 1/Z_H(x_i) = 1/(g^n w4^(i n) - 1), by i mod 4
+  quot_x_tables(power, x_lo, root_hi, zh_inv, s);
   hipLaunchKernelGGL(k_root_n, dim3(grid_for(n, kT, 1u << 30)), dim3(kT), 0, s, w_h.p, root_lo.p, root_hi.p,
                      (size_t)n);
   NZ_HIP(hipGetLastError());
-  // coset g*<w4>, g = 5 (the Fr multiplicative generator, ffjavascript's nqr): x_i = g*w4^i,
-  // g^j and g^-j for coset (un)scaling, and 1/Z_H(x_i) = 1/(g^n w4^(i n) - 1), by i mod 4
   const Fr g = fr_small(5), gi = inverse(g);
-  table(x_lo, nlo, w4, g);
   table(g_lo, nlo, g, one);
   table(g_hi, nhi, pow_u64(g, 4096), one);
   table(gi_lo, nlo, gi, one);
@@ -1301,13 +1510,6 @@ Prover::Prover(const uint8_t* zkey_bytes, size_t len, int device) {
                          gi_hi.p, inverse(pow_u64(two, (uint64_t)power + 2)), (size_t)n4);
     }
     NZ_HIP(hipGetLastError());
-  }
-  {
-    Fr gn = pow_u64(g, n), w4n = pow_u64(w4, n), p = gn;
-    for (int k = 0; k < 4; k++) {
-      zh_inv[k] = inverse(p - one);
-      p = p * w4n;
-    }
   }
   alloc_workspace();
   if (quot3) {  // the gate check on H reads the selectors on H contiguously (k_gate_h)
@@ -1359,14 +1561,7 @@ Prover::Prover(const uint8_t* zkey_bytes, size_t len, int device) {
     for (int k = 0; k < 3; k++) coset3(sigma.p + (size_t)k * 5 * n, cs3.p + (size_t)k * n3);
     for (uint32_t j = 0; j < nl; j++) coset3(lagrange.p + (size_t)j * 5 * n, cl3.p + (size_t)j * n3);
     NZ_HIP(hipGetLastError());
-    auto scale = [&](Fr* p, size_t m, int e) {
-      hipLaunchKernelGGL(k_dbl_pow, dim3(grid_for(m, kT, 1u << 30)), dim3(kT), 0, s, p, m, e);
-    };
-    scale(cq3.p, n3, 10);             // qm
-    scale(cq3.p + n3, 3 * n3, 5);     // ql, qr, qo
-    scale(cl3.p, (size_t)nl * n3, 5); // L_j
-    scale(x_lo.p, nlo, 5);            // g w4^j
-    NZ_HIP(hipGetLastError());
+    quot29_prescale(cq3.p, cl3.p, nl, n3, x_lo.p, s);
   } else {
     const uint32_t nl = nPublic > 0 ? nPublic : 1;
     cq.alloc((size_t)5 * n4);
@@ -1383,16 +1578,7 @@ Prover::Prover(const uint8_t* zkey_bytes, size_t len, int device) {
     for (int k = 0; k < 3; k++) coset_eval(sigma.p + (size_t)k * 5 * n, cs.p + (size_t)k * n4);
     for (uint32_t j = 0; j < nl; j++) coset_eval(lagrange.p + (size_t)j * 5 * n, cl.p + (size_t)j * n4);
     NZ_HIP(hipGetLastError());
-    if (nPublic <= kQ29MaxPub) {  // exponent pre-scaling of the 29-bit quotient (k_quotient_coset29)
-      auto scale = [&](Fr* p, size_t m, int e) {
-        hipLaunchKernelGGL(k_dbl_pow, dim3(grid_for(m, kT, 1u << 30)), dim3(kT), 0, s, p, m, e);
-      };
-      scale(cq.p, n4, 10);                      // qm
-      scale(cq.p + n4, 3 * n4, 5);              // ql, qr, qo
-      scale(cl.p, (size_t)nl * n4, 5);          // L_j
-      scale(x_lo.p, nlo, 5);                    // g w4^j
-      NZ_HIP(hipGetLastError());
-    }
+    if (nPublic <= kQ29MaxPub) quot29_prescale(cq.p, cl.p, nl, n4, x_lo.p, s);
   }
   NZ_HIP(hipStreamSynchronize(s));
 }
@@ -1563,26 +1749,13 @@ void Prover::copy_tops(hipStream_t s) {
 }
 
 void Prover::round3_quot3(const Fr& beta, const Fr& gamma, const Fr& alpha, hipStream_t s) {
-  const size_t n3 = (size_t)3 * n;
   // Lagrange commitments: round 1 ran the gate check on aux[2] (s waits for side_done), so
   // the one host round trip (tops and flag) comes first, while the GPU is idle anyway, and
   // none sits between the quotient and t's recombination
   const bool side = lcommit;
   if (side) copy_tops(s);
-  QArgs29 q29;
-  q29.beta = f29_exp(beta, 5);
-  q29.k23 = k1 == fr_small(2) && k2 == fr_small(3) ? 1 : 0;
-  q29.bk1 = f29_exp(beta * k1, 5);
-  q29.bk2 = f29_exp(beta * k2, 5);
-  q29.alpha2 = f29_exp(alpha * alpha, 5);
-  for (int k = 0; k < 4; k++) q29.zhinv[k] = f29_exp(zh_inv[k], 5);  // (unread: 1/Z_H is in itw3)
-  q29.gamma = f29_exp(gamma, 0);
-  q29.negone = f29_exp(neg(Fr::one()), 0);
-  q29.alpha = f29_exp(alpha, 20);
-  if (q29.k23)
-    hipLaunchKernelGGL(k_beta_xlo, dim3(grid_for(4096, kT)), dim3(kT), 0, s, x_lo.p, q29.beta, (size_t)4096, bx_lo.p);
-  hipLaunchKernelGGL((k_quotient_coset29<true>), dim3(grid_for(n3, kT, 1u << 30)), dim3(kT), 0, s, A4.p, B4.p, C4.p,
-                     Z4.p, cq3.p, cs3.p, cl3.p, nPublic, A.p, (size_t)n, x_lo.p, root_hi.p, bx_lo.p, q29, T.p);
+  quot_launch(true, A4.p, B4.p, C4.p, Z4.p, cq3.p, cs3.p, cl3.p, nPublic, A.p, (size_t)n, x_lo.p, root_hi.p, bx_lo.p,
+              beta, gamma, alpha, k1, k2, zh_inv, T.p, s);
   if (!side) launch_gate_check(s);
   for (int j = 0; j < 3; j++) {  // v_j = (t mod (X^n - d_j)) / 4
     NttIo io;
@@ -1892,42 +2065,12 @@ void Prover::set_msm_split(int world, size_t own_points, size_t own_lagrange, nz
 
 void Prover::eval_many(int np, const Fr* const* polys, const size_t* lens, const Fr* xs, Fr* out,
                        const std::function<void()>& overlap) {
-  if (np < 1 || np > kEvalMax) throw Error(NZCB_ERR_INTERNAL, "eval_many: bad count");
   hipStream_t s = st();
-  EvalSet es{};
-  size_t maxlen = 0;
-  for (int j = 0; j < np; j++) {
-    es.p[j] = polys[j];
-    es.len[j] = lens[j];
-    es.x[j] = xs[j];
-    es.x29[j] = fr29_operand(xs[j]);
-    es.y29[j] = fr29_operand(pow_u64(xs[j], kT));
-    es.x4096[j] = pow_u64(xs[j], (uint64_t)kT * kEvalChunk2);
-    maxlen = std::max(maxlen, lens[j]);
-  }
-  es.np = np;
-  const size_t nblocks = (maxlen + (size_t)kT * kEvalChunk2 - 1) / ((size_t)kT * kEvalChunk2);
-  if (nblocks > ((size_t)1 << kEvalBits)) throw Error(NZCB_ERR_INTERNAL, "eval_many: polynomial too long");
-  es.nbits = 1;
-  while (((size_t)1 << es.nbits) < nblocks) es.nbits++;
+  size_t nblocks = 0;
+  const EvalSet es = eval_set(np, polys, lens, xs, &nblocks);
   if ((size_t)np * nblocks + kEvalMax > eval_part.n) throw Error(NZCB_ERR_INTERNAL, "eval partial buffer too small");
-  Fr* res = eval_part.p + (size_t)np * nblocks;
-  F29* pw = eval_pw.p;
-  Fr* pw2 = (Fr*)(eval_pw.p + (size_t)kEvalMax * kT);
-  hipLaunchKernelGGL(k_eval_pows, dim3((unsigned)np), dim3(kT), 0, s, es, pw, pw2);
-  if (np == 7)
-    hipLaunchKernelGGL(k_eval_multi<7>, dim3((unsigned)nblocks), dim3(kT), 0, s, es, (const F29*)pw, (const Fr*)pw2,
-                       eval_part.p, (int)nblocks);
-  else if (np == 1)
-    hipLaunchKernelGGL(k_eval_multi<1>, dim3((unsigned)nblocks), dim3(kT), 0, s, es, (const F29*)pw, (const Fr*)pw2,
-                       eval_part.p, (int)nblocks);
-  else
-    throw Error(NZCB_ERR_INTERNAL, "eval_many: 1 or 7 evaluations");
-  NZ_HIP(hipGetLastError());
-  (void)res;
-  hipLaunchKernelGGL(k_eval_sum, dim3(np), dim3(kT), 0, s, (const Fr*)eval_part.p, (int)nblocks,
-                     top_host + kMbEvals);  // the mailbox
-  NZ_HIP(hipGetLastError());
+  eval_launch(es, nblocks, eval_part.p, eval_pw.p, (Fr*)(eval_pw.p + (size_t)kEvalMax * kT),
+              top_host + kMbEvals, s);  // the mailbox
   if (overlap) overlap();  // host work beside the evaluation kernels
   NZ_HIP(hipStreamSynchronize(s));
   for (int j = 0; j < np; j++) out[j] = top_host[kMbEvals + j];
@@ -1936,40 +2079,16 @@ void Prover::eval_many(int np, const Fr* const* polys, const size_t* lens, const
 // divPol1's power tables for d (k_lin_tile's LinTab) into slot k of lin_tab: host products,
 // uploaded on stream s (round 4 builds both on aux[2] while its evaluations run)
 void Prover::lin_tables(int k, const Fr& d, hipStream_t s) {
-  LinTab& t = ((LinTab*)lin_host.data())[k];
-  t.dp[0] = Fr::one();
-  for (int j = 1; j <= kPer; j++) t.dp[j] = t.dp[j - 1] * d;
-  const Fr dk = t.dp[kPer], dki = inverse(dk);  // inverse(0) = 0: Pinv = 0 past t = 0
-  t.P[0] = t.Pinv[0] = Fr::one();
-  for (int i = 1; i <= kT; i++) {
-    t.P[i] = t.P[i - 1] * dk;
-    t.Pinv[i] = t.Pinv[i - 1] * dki;
-  }
-  NZ_HIP(hipMemcpyAsync((LinTab*)lin_tab.p + k, &t, sizeof(LinTab), hipMemcpyHostToDevice, s));
-  Fr* q = lin_tile_pows(k);
-  const int qn = (int)lin_qn;
-  hipLaunchKernelGGL(k_pow_tiles, dim3((qn + 255) / 256), dim3(256), 0, s, t.P[kT], t.Pinv[kT], qn, q, q + qn);
-  NZ_HIP(hipGetLastError());
+  lin_tables_build(((LinTab*)lin_host.data())[k], d, (LinTab*)lin_tab.p + k, lin_tile_pows(k), (int)lin_qn, s);
 }
 
 Fr* Prover::lin_tile_pows(int k) { return lin_tab.p + 2 * sizeof(LinTab) / sizeof(Fr) + (size_t)k * 2 * lin_qn; }
 
 void Prover::div_pol1(const Fr* src, size_t m, int tab, const Fr& p0_adjust, Fr* dst, uint32_t flag_bit) {
-  hipStream_t s = st();
-  const size_t ntiles = (m + kTileN - 1) / kTileN;
-  const LinTab* lt = (const LinTab*)lin_tab.p + tab;
   const LinTab& ht = ((const LinTab*)lin_host.data())[tab];
-  if (ntiles + 1 > lin_qn) throw Error(NZCB_ERR_INTERNAL, "divPol1: more tiles than its power tables");
-  Fr* heads = scan_tmp.p;  // ntiles + 1 (the last one 0: the carry into the last tile)
-  hipLaunchKernelGGL(k_lin_tile<false>, dim3((unsigned)ntiles), dim3(kT), 0, s, src, m, lt, (const Fr*)nullptr, heads);
-  // true heads: H_T = h_T + d^kTileN H_(T+1), by the tile power tables (additions)
-  const Fr* q = lin_tile_pows(tab);
-  hipLaunchKernelGGL(k_tile_heads, dim3(1), dim3(1024), 0, s, heads, (int)ntiles, q, q + lin_qn);
-  NZ_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_lin_tile<true>, dim3((unsigned)ntiles), dim3(kT), 0, s, src, m, lt, (const Fr*)heads, dst);
-  hipLaunchKernelGGL(k_div_check, dim3(1), dim3(64), 0, s, src, p0_adjust, dst, ht.dp[1], flags.p, flag_bit,
-                     (uint32_t*)(top_host + kMbFlags));
-  NZ_HIP(hipGetLastError());
+  // heads: scan_tmp, lin_tiles(m) + 1 words (the last one 0: the carry into the last tile)
+  div_pol1_launch(src, m, (const LinTab*)lin_tab.p + tab, ht.dp[1], lin_tile_pows(tab), lin_qn, scan_tmp.p, p0_adjust,
+                  dst, flags.p, flag_bit, (uint32_t*)(top_host + kMbFlags), st());
 }
 
 // ----------------------------------------------------------------------------
@@ -2181,34 +2300,19 @@ void Prover::prove(const uint8_t* witness, size_t n_witness, const uint8_t* blin
     lg("gamma: " + fr_dec(gamma));
   }
   {
-    PermArgs pa;
-    shoup_pair(beta, pa.beta, pa.beta_s);
-    shoup_pair(k1 * beta, pa.k1beta, pa.k1beta_s);
-    shoup_pair(k2 * beta, pa.k2beta, pa.k2beta_s);
-    pa.gamma256 = f29_exp(gamma, 0);
-    pa.k23 = k1 == fr_small(2) && k2 == fr_small(3) ? 1 : 0;
+    bool generic_k = false;
     if (fault == NZCB_DEBUG_GENERIC_K) {  // nzcb_debug_inject_fault: the k1, k2 products path, once
       fault = 0;
-      pa.k23 = 0;
+      generic_k = true;
     }
-    const size_t ntiles = (n + kTileN - 1) / kTileN;
-    if (ntiles > 1024 * 64) throw Error(NZCB_ERR_INTERNAL, "round 2: domain too large for the tile factors");
-    Fr* ntot = scan_tmp.p;  // per tile: numerator / denominator totals, then the factors F_T
-    Fr* dtot = ntot + ntiles;
-    Fr* fac = dtot + ntiles;
-    Fr* totals = fac + ntiles;
-    hipLaunchKernelGGL(k_perm_tile, dim3((unsigned)ntiles), dim3(kT), 0, s, A.p, B.p, C.p, sig_h.p, (size_t)n,
-                       w_h.p, pa, Z.p, ntot, dtot);
-    hipLaunchKernelGGL(k_perm_factors, dim3(1), dim3(1024), 0, s, (const Fr*)ntot, (const Fr*)dtot, (int)ntiles,
-                       fac, top_host + kMbTotals);
-    NZ_HIP(hipGetLastError());
+    const PermArgs pa = perm_args(beta, gamma, k1, k2, generic_k);
+    // scan_tmp: per tile the numerator / denominator totals, then the factors F_T
+    perm_launch(A.p, B.p, C.p, sig_h.p, (size_t)n, w_h.p, pa, Z.p, scan_tmp.p, top_host + kMbTotals, s);
     // Z[n] = prod num / prod den must be 1; 1 / prod den scales the tiles
     NZ_HIP(hipStreamSynchronize(s));
     const Fr tt[2] = {top_host[kMbTotals], top_host[kMbTotals + 1]};
     if (tt[0] != tt[1]) throw Error(NZCB_ERR_COPY, "Copy constraints does not match");
-    hipLaunchKernelGGL(k_apply_tiles, dim3((unsigned)ntiles), dim3(kT), 0, s, Z.p, (size_t)n,
-                       (const Fr*)fac, inverse(tt[1]));
-    NZ_HIP(hipGetLastError());
+    perm_apply(Z.p, (size_t)n, scan_tmp.p, tt[1], s);
     const int bz[3] = {9, 8, 7};
     // Z's transforms use their own scratch (ntt_scr2), so they need not wait for A, B, C's
     // on aux[2] (round 3 does). Z's commitment needs only its coefficients: its MSM starts
@@ -2232,37 +2336,14 @@ void Prover::prove(const uint8_t* witness, size_t n_witness, const uint8_t* blin
     lg("alpha: " + fr_dec(alpha));
   }
   {
-    QArgs q;
-    q.beta = beta;
-    q.gamma = gamma;
-    q.alpha = alpha;
-    q.alpha2 = alpha * alpha;
-    q.bk1 = beta * k1;
-    q.bk2 = beta * k2;
-    for (int k = 0; k < 4; k++) q.zhinv[k] = zh_inv[k];
     auto tq = std::chrono::steady_clock::now();
     NZ_HIP(hipStreamWaitEvent(s, side_done, 0));  // A, B, C's coset evaluations (aux[2], round 1)
     if (quot3) {
       round3_quot3(beta, gamma, alpha, s);
-    } else if (nPublic <= kQ29MaxPub) {
-      QArgs29 q29;
-      q29.beta = f29_exp(beta, 5);
-      q29.k23 = k1 == fr_small(2) && k2 == fr_small(3) ? 1 : 0;
-      q29.bk1 = f29_exp(q.bk1, 5);
-      q29.bk2 = f29_exp(q.bk2, 5);
-      q29.alpha2 = f29_exp(q.alpha2, 5);
-      for (int k = 0; k < 4; k++) q29.zhinv[k] = f29_exp(zh_inv[k], 5);
-      q29.gamma = f29_exp(gamma, 0);
-      q29.negone = f29_exp(neg(Fr::one()), 0);
-      q29.alpha = f29_exp(alpha, 20);
-      hipLaunchKernelGGL((k_quotient_coset29<false>), dim3(grid_for(n4, kT, 1u << 30)), dim3(kT), 0, s, A4.p, B4.p,
-                         C4.p, Z4.p, cq.p, cs.p, cl.p, nPublic, A.p, (size_t)n, x_lo.p, root_hi.p, (const Fr*)nullptr, q29,
-                         T.p);
-    } else {
-      hipLaunchKernelGGL(k_quotient_coset, dim3(grid_for(n4, kT, 1u << 30)), dim3(kT), 0, s, A4.p, B4.p, C4.p,
-                         Z4.p, cq.p, cs.p, cl.p, nPublic, A.p, (size_t)n, x_lo.p, root_hi.p, q, T.p);
+    } else {  // the 4n coset: the 9x29 kernel up to kQ29MaxPub public inputs, else the 8x32 one
+      quot_launch(false, A4.p, B4.p, C4.p, Z4.p, cq.p, cs.p, cl.p, nPublic, A.p, (size_t)n, x_lo.p, root_hi.p, nullptr,
+                  beta, gamma, alpha, k1, k2, zh_inv, T.p, s);
     }
-    NZ_HIP(hipGetLastError());
     if (!quot3) {
       NttIo io;  // 1/4n, the coset unscale g^-j and the degree check fused into the iNTT's last pass
       io.out_f = gi29.p;
@@ -2426,4 +2507,196 @@ void Prover::prove(const uint8_t* witness, size_t n_witness, const uint8_t* blin
   }
 }
 
+// ----------------------------------------------------------------------------
+// kernel-level entries (include/nzcb_internal.h): the round 2-5 kernels alone, through the
+// launch helpers above, over host arrays of canonical 32-byte LE Montgomery words
+// ----------------------------------------------------------------------------
+namespace {
+
+constexpr size_t kDebugMax = (size_t)1 << 26;  // elements per array
+
+void need_canonical(const uint8_t* p, size_t count, const char* what) {
+  for (size_t i = 0; i < count; i++) {
+    Fr x;
+    std::memcpy(x.v, p + 32 * i, 32);
+    if (reduce_once(x) != x) throw Error(NZCB_ERR_ARG, std::string(what) + ": a word is not below r");
+  }
+}
+Fr lem_word(const uint8_t* p, const char* what) {
+  need_canonical(p, 1, what);
+  Fr x;
+  std::memcpy(x.v, p, 32);
+  return x;
+}
+
+// `count` words of a host array on the call's device
+Fr* upload(CallScope& cs, const uint8_t* src, size_t count) {
+  Fr* d = cs.alloc<Fr>(count * sizeof(Fr));
+  if (count) NZ_HIP(hipMemcpyAsync(d, src, count * sizeof(Fr), hipMemcpyHostToDevice, cs.st));
+  return d;
+}
+
+// what the kernels write for the host (Prover::top_host): coherent pinned words
+struct Mailbox {
+  Fr* p = nullptr;
+  explicit Mailbox(size_t words) {
+    NZ_HIP(hipHostMalloc((void**)&p, words * sizeof(Fr), hipHostMallocCoherent));
+    std::memset((void*)p, 0, words * sizeof(Fr));
+  }
+  ~Mailbox() {
+    if (p) (void)hipHostFree(p);
+  }
+  Mailbox(const Mailbox&) = delete;
+  Mailbox& operator=(const Mailbox&) = delete;
+};
+
+void debug_grand_product(int device, const uint8_t* abc, const uint8_t* sigma, const uint8_t* x, size_t n,
+                         const uint8_t* beta, const uint8_t* gamma, const uint8_t* k1, const uint8_t* k2, int generic_k,
+                         uint8_t* z_out, uint8_t* totals_out) {
+  if (!abc || !sigma || !x || !beta || !gamma || !k1 || !k2 || !z_out || !totals_out || n < 1 || n > kDebugMax)
+    throw Error(NZCB_ERR_ARG, "grand product: null argument or n outside 1..2^26");
+  need_canonical(abc, 3 * n, "grand product: abc");
+  need_canonical(sigma, 3 * n, "grand product: sigma");
+  need_canonical(x, n, "grand product: x");
+  const Fr b = lem_word(beta, "grand product: beta"), g = lem_word(gamma, "grand product: gamma");
+  const Fr f1 = lem_word(k1, "grand product: k1"), f2 = lem_word(k2, "grand product: k2");
+  CallScope cs(device, nullptr, 0);
+  Mailbox mail(2);
+  const Fr* dabc = upload(cs, abc, 3 * n);
+  const Fr* dsig = upload(cs, sigma, 3 * n);
+  const Fr* dx = upload(cs, x, n);
+  Fr* dz = cs.alloc<Fr>(n * sizeof(Fr));
+  Fr* scan = cs.alloc<Fr>(3 * perm_tiles(n) * sizeof(Fr));
+  perm_launch(dabc, dabc + n, dabc + 2 * n, dsig, n, dx, perm_args(b, g, f1, f2, generic_k != 0), dz, scan, mail.p,
+              cs.st);
+  NZ_HIP(hipStreamSynchronize(cs.st));
+  const Fr tt[2] = {mail.p[0], mail.p[1]};
+  perm_apply(dz, n, scan, tt[1], cs.st);
+  NZ_HIP(hipMemcpyAsync(z_out, dz, n * sizeof(Fr), hipMemcpyDeviceToHost, cs.st));
+  NZ_HIP(hipStreamSynchronize(cs.st));
+  std::memcpy(totals_out, tt, sizeof(tt));
+}
+
+void debug_div_pol1(int device, const uint8_t* p, size_t m, const uint8_t* d, const uint8_t* p0_adjust, uint8_t* q_out,
+                    int* divides_out) {
+  if (!p || !d || !p0_adjust || !q_out || !divides_out || m < 2 || m > kDebugMax)
+    throw Error(NZCB_ERR_ARG, "divPol1: null argument or m outside 2..2^26");
+  need_canonical(p, m, "divPol1: p");
+  const Fr dv = lem_word(d, "divPol1: d"), adj = lem_word(p0_adjust, "divPol1: p0_adjust");
+  LinTab host;  // outlives the call scope, which drains the stream that copies it
+  CallScope cs(device, nullptr, 0);
+  Mailbox mail(1);
+  const Fr* src = upload(cs, p, m);
+  const size_t qn = lin_tiles(m) + 2;
+  LinTab* lt = cs.alloc<LinTab>(sizeof(LinTab));
+  Fr* q = cs.alloc<Fr>(2 * qn * sizeof(Fr));
+  Fr* heads = cs.alloc<Fr>((lin_tiles(m) + 1) * sizeof(Fr));
+  Fr* dst = cs.alloc<Fr>(m * sizeof(Fr));
+  uint32_t* flags = cs.alloc<uint32_t>(sizeof(uint32_t));
+  NZ_HIP(hipMemsetAsync(flags, 0, sizeof(uint32_t), cs.st));
+  lin_tables_build(host, dv, lt, q, (int)qn, cs.st);
+  div_pol1_launch(src, m, lt, dv, q, qn, heads, adj, dst, flags, 4u, (uint32_t*)mail.p, cs.st);
+  NZ_HIP(hipMemcpyAsync(q_out, dst, m * sizeof(Fr), hipMemcpyDeviceToHost, cs.st));
+  NZ_HIP(hipStreamSynchronize(cs.st));
+  *divides_out = (mail.p[0].v[0] & 4u) ? 0 : 1;
+}
+
+void debug_eval_many(int device, int np, const uint8_t* const* polys, const size_t* lens, const uint8_t* xs,
+                     uint8_t* out) {
+  if ((np != 1 && np != 7) || !polys || !lens || !xs || !out)
+    throw Error(NZCB_ERR_ARG, "evaluations: null argument or np not 1 or 7");
+  for (int j = 0; j < np; j++) {
+    if (!polys[j] || lens[j] < 1 || lens[j] > kDebugMax)
+      throw Error(NZCB_ERR_ARG, "evaluations: null polynomial or length outside 1..2^26");
+    need_canonical(polys[j], lens[j], "evaluations: coefficients");
+  }
+  need_canonical(xs, (size_t)np, "evaluations: xs");
+  CallScope cs(device, nullptr, 0);
+  Mailbox mail(kEvalMax);
+  const Fr* dp[kEvalMax];
+  Fr xv[kEvalMax];
+  for (int j = 0; j < np; j++) {
+    dp[j] = upload(cs, polys[j], lens[j]);
+    std::memcpy(xv[j].v, xs + 32 * (size_t)j, 32);
+  }
+  size_t nblocks = 0;
+  const EvalSet es = eval_set(np, dp, lens, xv, &nblocks);
+  Fr* part = cs.alloc<Fr>((size_t)np * nblocks * sizeof(Fr));
+  F29* pw = cs.alloc<F29>((size_t)kEvalMax * kT * sizeof(F29));
+  Fr* pw2 = cs.alloc<Fr>((size_t)kEvalMax * kEvalBits * sizeof(Fr));
+  eval_launch(es, nblocks, part, pw, pw2, mail.p, cs.st);
+  NZ_HIP(hipStreamSynchronize(cs.st));
+  std::memcpy(out, mail.p, (size_t)np * sizeof(Fr));
+}
+
+void debug_quotient(int device, int power, int three, uint32_t npub, const uint8_t* abcz, const uint8_t* q,
+                    const uint8_t* sg, const uint8_t* l, const uint8_t* apub, const uint8_t* beta, const uint8_t* gamma,
+                    const uint8_t* alpha, const uint8_t* k1, const uint8_t* k2, uint8_t* t_out) {
+  if (!abcz || !q || !sg || !l || (npub && !apub) || !beta || !gamma || !alpha || !k1 || !k2 || !t_out || power < 2 ||
+      power > 24 || npub > 64)
+    throw Error(NZCB_ERR_ARG, "quotient: null argument, power outside 2..24 or more than 64 public inputs");
+  if (three && npub > kQ29MaxPub)
+    throw Error(NZCB_ERR_ARG, "quotient: the three-coset form takes at most 8 public inputs");
+  const size_t n = (size_t)1 << power, P = (three ? 3 : 4) * n;
+  const uint32_t nl = npub > 0 ? npub : 1;
+  need_canonical(abcz, 4 * P, "quotient: abcz");
+  need_canonical(q, 5 * P, "quotient: q");
+  need_canonical(sg, 3 * P, "quotient: s");
+  need_canonical(l, nl * P, "quotient: l");
+  need_canonical(apub, npub, "quotient: apub");
+  const Fr b = lem_word(beta, "quotient: beta"), g = lem_word(gamma, "quotient: gamma");
+  const Fr a = lem_word(alpha, "quotient: alpha");
+  const Fr f1 = lem_word(k1, "quotient: k1"), f2 = lem_word(k2, "quotient: k2");
+  CallScope cs(device, nullptr, 0);
+  const Fr* dabcz = upload(cs, abcz, 4 * P);
+  Fr* dq = upload(cs, q, 5 * P);
+  const Fr* ds = upload(cs, sg, 3 * P);
+  Fr* dl = upload(cs, l, nl * P);
+  const Fr* dapub = upload(cs, apub, npub);
+  Fr* bx_lo = three ? cs.alloc<Fr>(4096 * sizeof(Fr)) : nullptr;
+  Fr* dt = cs.alloc<Fr>(P * sizeof(Fr));
+  DevBuf<Fr> x_lo, root_hi;
+  Fr zh_inv[4];
+  try {
+    quot_x_tables(power, x_lo, root_hi, zh_inv, cs.st);
+    if (npub <= kQ29MaxPub) quot29_prescale(dq, dl, nl, P, x_lo.p, cs.st);
+    quot_launch(three != 0, dabcz, dabcz + P, dabcz + 2 * P, dabcz + 3 * P, dq, ds, dl, npub, dapub, n, x_lo.p, root_hi.p,
+                bx_lo, b, g, a, f1, f2, zh_inv, dt, cs.st);
+    NZ_HIP(hipMemcpyAsync(t_out, dt, P * sizeof(Fr), hipMemcpyDeviceToHost, cs.st));
+    NZ_HIP(hipStreamSynchronize(cs.st));
+  } catch (...) {
+    (void)hipStreamSynchronize(cs.st);  // x_lo, root_hi are freed before the call scope drains its stream
+    throw;
+  }
+}
+
+}  // namespace
+
 }  // namespace nzcb
+
+using namespace nzcb;
+
+extern "C" int nzcb_debug_grand_product(int device, const uint8_t* abc, const uint8_t* sigma, const uint8_t* x, size_t n,
+                                        const uint8_t* beta, const uint8_t* gamma, const uint8_t* k1, const uint8_t* k2,
+                                        int generic_k, uint8_t* z_out, uint8_t* totals_out, nzcb_err* err) {
+  return guarded(err, [&] { debug_grand_product(device, abc, sigma, x, n, beta, gamma, k1, k2, generic_k, z_out, totals_out); });
+}
+
+extern "C" int nzcb_debug_div_pol1(int device, const uint8_t* p, size_t m, const uint8_t* d, const uint8_t* p0_adjust,
+                                   uint8_t* q_out, int* divides_out, nzcb_err* err) {
+  return guarded(err, [&] { debug_div_pol1(device, p, m, d, p0_adjust, q_out, divides_out); });
+}
+
+extern "C" int nzcb_debug_eval_many(int device, int np, const uint8_t* const* polys, const size_t* lens,
+                                    const uint8_t* xs, uint8_t* out, nzcb_err* err) {
+  return guarded(err, [&] { debug_eval_many(device, np, polys, lens, xs, out); });
+}
+
+extern "C" int nzcb_debug_quotient(int device, int power, int three, uint32_t npub, const uint8_t* abcz,
+                                   const uint8_t* q, const uint8_t* s, const uint8_t* l, const uint8_t* apub,
+                                   const uint8_t* beta, const uint8_t* gamma, const uint8_t* alpha, const uint8_t* k1,
+                                   const uint8_t* k2, uint8_t* t_out, nzcb_err* err) {
+  return guarded(err, [&] {
+    debug_quotient(device, power, three, npub, abcz, q, s, l, apub, beta, gamma, alpha, k1, k2, t_out);
+  });
+}

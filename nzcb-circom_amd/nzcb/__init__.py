@@ -62,6 +62,7 @@ EXPORTED_SYMBOLS = [
     "nzcb_groth16_vk_to_json", "nzcb_groth16_vk_to_json_file", "nzcb_engine_groth16_rows",
     "nzcb_debug_groth16_schedule", "nzcb_debug_groth16_timings",
     "nzcb_debug_signal_basis_cap", "nzcb_debug_signal_basis_info", "nzcb_debug_commit_abc", "nzcb_debug_signal_rows",
+    "nzcb_debug_grand_product", "nzcb_debug_div_pol1", "nzcb_debug_eval_many", "nzcb_debug_quotient",
 ]
 
 NZCB_FAULT_QUOTIENT = 1  # include/nzcb_internal.h
@@ -129,6 +130,54 @@ def f29_check(op: int, words, device: int = 0):
     err = _Err()
     _check(load().nzcb_debug_f29(device, op, arr, count, out, ctypes.byref(err)), err)
     return list(out)[:count * wout]
+
+
+def debug_grand_product(abc: bytes, sigma: bytes, x: bytes, beta: bytes, gamma: bytes, k1: bytes, k2: bytes,
+                        generic_k: bool = False, device: int = 0):
+    """Round 2's kernels alone (include/nzcb_internal.h nzcb_debug_grand_product): abc, sigma = 3
+    columns of n words, x = n words, all 32-byte LE Montgomery. Returns (z, totals) as bytes."""
+    n = len(x) // 32
+    assert len(x) == 32 * n and len(abc) == 96 * n and len(sigma) == 96 * n
+    z, tot, err = _out(32 * n), _out(64), _Err()
+    _check(load().nzcb_debug_grand_product(device, abc, sigma, x, n, beta, gamma, k1, k2, int(generic_k), z, tot,
+                                           ctypes.byref(err)), err)
+    return bytes(z)[:32 * n], bytes(tot)
+
+
+def debug_div_pol1(p: bytes, d: bytes, p0_adjust: bytes = bytes(32), device: int = 0):
+    """Round 5's divPol1 kernels alone (nzcb_debug_div_pol1) over m = len(p) / 32 coefficients.
+    Returns (q, divides): the m quotient words and whether the division check held."""
+    m = len(p) // 32
+    assert len(p) == 32 * m
+    q, ok, err = _out(32 * m), c_int(-1), _Err()
+    _check(load().nzcb_debug_div_pol1(device, p, m, d, p0_adjust, q, ctypes.byref(ok), ctypes.byref(err)), err)
+    return bytes(q)[:32 * m], bool(ok.value)
+
+
+def debug_eval_many(polys, xs: bytes, device: int = 0) -> bytes:
+    """Round 4's evaluation kernels alone (nzcb_debug_eval_many): polys = 1 or 7 byte strings of
+    coefficients, xs = one point each. Returns the evaluations, 32 bytes each."""
+    np_ = len(polys)
+    assert len(xs) == 32 * np_ and all(len(p) % 32 == 0 for p in polys)
+    arr = (ctypes.c_char_p * max(np_, 1))(*polys)
+    lens = (c_size_t * max(np_, 1))(*[len(p) // 32 for p in polys])
+    out, err = _out(32 * np_), _Err()
+    _check(load().nzcb_debug_eval_many(device, np_, arr, lens, xs, out, ctypes.byref(err)), err)
+    return bytes(out)[:32 * np_]
+
+
+def debug_quotient(power: int, three: bool, npub: int, abcz: bytes, q: bytes, s: bytes, l: bytes, apub: bytes,
+                   beta: bytes, gamma: bytes, alpha: bytes, k1: bytes, k2: bytes, device: int = 0) -> bytes:
+    """Round 3's quotient kernels alone (nzcb_debug_quotient) over P = 3n (three) or 4n points of
+    the domain n = 2^power: abcz, q, s, l = 4, 5, 3, max(npub, 1) columns of P words. Returns the
+    P words the kernel stores."""
+    pts = (3 if three else 4) << power
+    assert len(abcz) == 128 * pts and len(q) == 160 * pts and len(s) == 96 * pts
+    assert len(l) == 32 * pts * max(npub, 1) and len(apub) == 32 * npub
+    out, err = _out(32 * pts), _Err()
+    _check(load().nzcb_debug_quotient(device, power, int(three), npub, abcz, q, s, l, apub, beta, gamma, alpha, k1, k2,
+                                      out, ctypes.byref(err)), err)
+    return bytes(out)[:32 * pts]
 
 
 def guard_selftest(device: int = 0) -> None:
@@ -369,6 +418,17 @@ def load(path: str | None = None):
         "nzcb_debug_signal_basis_info": (c_int, [c_void_p, POINTER(c_uint64)]),
         "nzcb_debug_commit_abc": (c_int, [c_void_p, u8p, c_size_t, u8p, c_int, u8p, POINTER(_Err)]),
         "nzcb_debug_signal_rows": (c_int, [c_void_p, c_int, u8p, POINTER(c_uint32), c_size_t, POINTER(_Err)]),
+        "nzcb_debug_grand_product": (c_int, [c_int, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, c_size_t,
+                                             ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, c_int,
+                                             u8p, u8p, POINTER(_Err)]),
+        "nzcb_debug_div_pol1": (c_int, [c_int, ctypes.c_char_p, c_size_t, ctypes.c_char_p, ctypes.c_char_p, u8p,
+                                        POINTER(c_int), POINTER(_Err)]),
+        "nzcb_debug_eval_many": (c_int, [c_int, c_int, POINTER(ctypes.c_char_p), POINTER(c_size_t), ctypes.c_char_p,
+                                         u8p, POINTER(_Err)]),
+        "nzcb_debug_quotient": (c_int, [c_int, c_int, c_int, c_uint32, ctypes.c_char_p, ctypes.c_char_p,
+                                        ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p,
+                                        ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, u8p,
+                                        POINTER(_Err)]),
     }
     lib.missing_symbols = []
     for name, (res, args) in sigs.items():

@@ -353,10 +353,12 @@ def prove(zk: dict, witness, blinding=None, transcript_pub: bool = True, trace: 
         pol_wxi[i] = acc % R_MOD
     pol_wxi[0] = (pol_wxi[0] - ev["t"] - v[1] * ev["r"] - v[2] * ev["a"] - v[3] * ev["b"] - v[4] * ev["c"]
                   - v[5] * ev["s1"] - v[6] * ev["s2"]) % R_MOD
+    wxi_num = list(pol_wxi)
     pol_wxi = _div_pol1(pol_wxi, xi)
     proof["Wxi"] = exp_tau(pol_wxi)
     pol_wxiw = list(pol_z[:n + 3])
     pol_wxiw[0] = (pol_wxiw[0] - ev["zw"]) % R_MOD
+    wxiw_num = list(pol_wxiw)
     pol_wxiw = _div_pol1(pol_wxiw, xi * wn % R_MOD)
     proof["Wxiw"] = exp_tau(pol_wxiw)
 
@@ -368,7 +370,8 @@ def prove(zk: dict, witness, blinding=None, transcript_pub: bool = True, trace: 
         trace["eval_t"] = ev["t"]
         trace.update({"pol_a": pol_a, "pol_b": pol_b, "pol_c": pol_c, "pol_z": pol_z, "pol_t": pol_t,
                       "pol_r": pol_r, "pol_wxi": pol_wxi, "pol_wxiw": pol_wxiw, "A4": A4, "Z4": Z4,
-                      "T": T, "Tz": Tz, "Z": Z, "A": A, "B": B, "C": C})
+                      "T": T, "Tz": Tz, "Z": Z, "A": A, "B": B, "C": C, "B4": B4, "C4": C4,
+                      "wxi_num": wxi_num, "wxiw_num": wxiw_num})
     return proof, public
 
 
